@@ -155,23 +155,36 @@ def _source_id_text(want):
             '}\n' % tree_sha())
 
 
+def _current(want):
+    """True when every object, the generated identity unit and the library are what the working tree builds (read-only)."""
+    id_src = os.path.join(LIBDIR, "source_id.cpp")
+    return (all(os.path.exists(obj) and _recorded(obj) == want[name] for name, _, obj, _ in _units())
+            and os.path.exists(id_src) and open(id_src).read() == _source_id_text(want)
+            and os.path.exists(os.path.join(LIBDIR, "source_id.o")) and os.path.exists(os.path.join(LIBDIR, "libartemis_hip.so")))
+
+
 def build_hip(force=False, verbose=False, only=None):
     """Bring lib/libartemis_hip.so up to date with the working tree and return its path.  Objects whose content hash is
     unchanged are kept.  only = ["kernels_curv.hip", ...] (development): assert that nothing else needs compiling --
-    the call REFUSES (RuntimeError) if an object outside the list is stale instead of linking it."""
-    os.makedirs(LIBDIR, exist_ok=True)
+    the call REFUSES (RuntimeError) if an object outside the list is stale instead of linking it.  An up-to-date tree
+    is not written to (no lock file either): a user who may not write to the checkout loads the library it holds."""
     target = os.path.join(LIBDIR, "libartemis_hip.so")
+    if not force:
+        want = object_hashes()
+        if _current(want):
+            return target
+        if only:
+            listed = {o.replace(".hip", "").replace(".cpp", "") for o in only}
+            outside = [name for name in stale_objects() if name not in listed and name.replace("driver_", "") not in listed]
+            if outside:
+                raise RuntimeError("build_hip(only=%s): %s are stale too (their sources, headers or flags changed); "
+                                   "refusing to link objects that are not the tree" % (only, outside))
+    os.makedirs(LIBDIR, exist_ok=True)
     with open(os.path.join(LIBDIR, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)  # (several ranks / test workers may call this at once)
         want = object_hashes()
         units = _units()
         todo = [u for u in units if force or not os.path.exists(u[2]) or _recorded(u[2]) != want[u[0]]]
-        if only:
-            listed = {o.replace(".hip", "").replace(".cpp", "") for o in only}
-            outside = [u[0] for u in todo if u[0] not in listed and u[0].replace("driver_", "") not in listed]
-            if outside and not force:
-                raise RuntimeError("build_hip(only=%s): %s are stale too (their sources, headers or flags changed); "
-                                   "refusing to link objects that are not the tree" % (only, outside))
         id_src = os.path.join(LIBDIR, "source_id.cpp")
         id_txt = _source_id_text(want)
         id_stale = (not os.path.exists(id_src)) or open(id_src).read() != id_txt or not os.path.exists(os.path.join(LIBDIR, "source_id.o"))

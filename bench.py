@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- zone-cycles/s of the Artemis hydro update on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: under a launcher (WORLD_SIZE set) this process is one rank; without one the
@@ -17,11 +17,15 @@ per rank, ranks cut along x3 then x2, never along x1: rank grid 1x1x2, 1x2x2, 1x
 ghost fill), the CFL reduction and, for N > 1, the halo exchange and the dt all-reduce.
 Initial data are generated on the host and are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (the fused stage
-kernel) with the ALGORITHMIC bytes of SURVEY.md section 8(d) -- 240 B per cell-stage -- over
-its HIP-event-timed launch duration; `cpu_baseline` times the CPU oracle (a restatement of
-the reference's CPU path, NOT the Artemis executable, which cannot be built here) on the host
-cores for a bounded sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the
+line: `value` and `ms_per_step` come from the timed steps alone.  --dump-outputs DIR also writes
+what the last timed step left a caller (dump_outputs()).  --full adds every measurement that
+takes runs of its own, after the timed steps: `roofline` prices the dominant kernel (the fused
+stage kernel) with the ALGORITHMIC bytes of SURVEY.md section 8(d) -- 240 B per cell-stage --
+over its HIP-event-timed launch duration (a separate leg with kernel timing on); `cpu_baseline`
+times the CPU oracle (a restatement of the reference's CPU path, NOT the Artemis executable,
+which cannot be built here) on the host cores for a bounded sample of the same workload; the
+Sedov line adds `dropin` and the overlap emulation, the disk_amr line its remesh legs.
 """
 import argparse
 import json
@@ -38,6 +42,8 @@ os.environ.setdefault("OMP_PLACES", "cores")
 
 ALG_BYTES_PER_CELL_STAGE = 240.0   # 30 doubles
 HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_FIELD_BYTES = 48 << 20        # --dump-outputs: the sampled fields of all ranks together stay below this
+DUMP_SEED = 1234                   # --dump-outputs: the zone sample is drawn from this seed (+ rank)
 
 
 # Rank grid (x1, x2, x3) per GPU count.  BASELINE.md 2.2 suggests 2x2x2 -> 512^3 at 8 GPUs; this bench keeps the same
@@ -275,6 +281,58 @@ def record_remesh(sim, events, what, call):
     return changed
 
 
+def load_library():
+    """capi.load() without writing to the checkout when its library is up to date: the build check is skipped and
+    build.verify() holds the library to the working tree instead (a checkout whose build_hip() opens its lock file even
+    with nothing to build then also runs for a user who may not write to it, so two builds of the project can be
+    measured and their outputs dumped by the same command).  A missing or stale library is built by capi.load()."""
+    from artemis_amd import build, capi
+    if (os.environ.get("ARTEMIS_NO_BUILD_CHECK") or not os.path.exists(os.path.join(build.LIBDIR, "libartemis_hip.so"))
+            or build.stale_objects()):
+        return capi.load()
+    os.environ["ARTEMIS_NO_BUILD_CHECK"] = "1"
+    try:
+        L = capi.load()
+    finally:
+        del os.environ["ARTEMIS_NO_BUILD_CHECK"]
+    build.verify(L)
+    return L
+
+
+def dump_outputs(sim, outdir, rank, world):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as float64 .npy files --
+    gas_prim (and dust_prim) = the primitive variables [nvar, nzones] at a fixed, seeded sample of this rank's interior
+    zones in block order (every zone when they fit: DUMP_FIELD_BYTES over all ranks), dt = the next step's timestep,
+    time, history = the conserved sums of sim.history().  An N-GPU run writes one set per rank, named <name>_rank<r>."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    fields = [("gas.prim", 6 * sim.ns_gas)] + ([("dust.prim", 4 * sim.ns_dust)] if sim.ns_dust else [])
+    shape = (sim.ke - sim.ks + 1, sim.je - sim.js + 1, sim.ie - sim.is_ + 1)
+    per_block = shape[0] * shape[1] * shape[2]
+    total = sim.nblocks * per_block
+    nsample = min(total, DUMP_FIELD_BYTES // world // (8 * sum(n for _, n in fields)))
+    if nsample < total:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(total, size=nsample, replace=False))
+    else:
+        idx = np.arange(total)
+    for name, _ in fields:
+        out = None
+        for b in range(sim.nblocks):
+            lo, hi = np.searchsorted(idx, (b * per_block, (b + 1) * per_block))
+            if lo == hi:
+                continue
+            a = sim.field(name, b)
+            k, j, i = np.unravel_index(idx[lo:hi] - b * per_block, shape)
+            if out is None:
+                out = np.empty((a.shape[0], len(idx)))
+            out[:, lo:hi] = a[:, sim.ks + k, sim.js + j, sim.is_ + i]
+        np.save(os.path.join(outdir, name.replace(".", "_") + sfx + ".npy"), out)
+    np.save(os.path.join(outdir, "dt" + sfx + ".npy"), np.array([sim.dt]))
+    np.save(os.path.join(outdir, "time" + sfx + ".npy"), np.array([sim.time]))
+    np.save(os.path.join(outdir, "history" + sfx + ".npy"), np.asarray(sim.history(), dtype=np.float64))
+
+
 def main():
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a version banner through C
     # stdio when a communicator is created): keep the caller's stdout for the line and send everything else that
@@ -285,12 +343,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--n", type=int, default=256, help="cells per GPU per dimension")
     ap.add_argument("--path", default="fused", choices=["fused", "unfused"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (dump_outputs())")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the measurements that take runs of their own: the kernel-timing "
+                         "leg of `roofline`, `cpu_baseline`, the Sedov `dropin` and overlap-emulation legs, the disk_amr "
+                         "remesh legs (the --no-* switches below leave single ones out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` leg")
     ap.add_argument("--no-dropin", action="store_true",
-                    help="skip the `dropin` legs (fused + cons + whole-block PrimToCons, and the per-task chain)")
+                    help="--full: skip the `dropin` legs (fused + cons + whole-block PrimToCons, and the per-task chain)")
     ap.add_argument("--no-overlap-emulation", action="store_true",
-                    help="skip the `overlap_emulation` leg (two half-size blocks, shell-first + bulk launches): profiles of "
-                         "the headline kernel then hold 256^3 launches only")
+                    help="--full: skip the `overlap_emulation` leg (two half-size blocks, shell-first + bulk launches): profiles "
+                         "of the headline kernel then hold 256^3 launches only")
     ap.add_argument("--no-overlap", action="store_true",
                     help="N > 1: exchange halos after the whole stage kernel instead of behind its bulk")
     ap.add_argument("--overlap-mode", type=int, default=1, choices=[1, 2],
@@ -304,7 +368,7 @@ def main():
                          "transport unless this is given")
     ap.add_argument("--loopback", action="store_true",
                     help="diagnostic: route block-to-block slabs of ONE GPU through RCCL send/recv-to-self")
-    ap.add_argument("--no-remesh-leg", action="store_true", help="disk_amr: skip the remesh measurements after the timed region")
+    ap.add_argument("--no-remesh-leg", action="store_true", help="disk_amr --full: skip the remesh measurements after the timed region")
     ap.add_argument("--remesh-in-timed-region", action="store_true",
                     help="disk_amr: inject the batched refinement tags of the remesh leg INSIDE the timed region (every "
                          "4th cycle ~2.5 %% of the leaves; the criterion merges them again derefine_count cycles later), so "
@@ -329,6 +393,8 @@ def main():
     ap.add_argument("--cpu-cycles", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = all host cores)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus not in DECOMPOSITION:
         raise SystemExit("--gpus must be 1, 2, 4 or 8")
     if args.gpus > 1 and args.workload in ("ssheet_dust", "disk_sph", "linwave3d"):
@@ -353,7 +419,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
     torch.cuda.set_device(local_rank)
-    L = capi.load()
+    L = load_library()
     capi.check(L.artemis_rt_set_device(local_rank))
     comm = None
     dist = None
@@ -546,8 +612,11 @@ def main():
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         elapsed = elapsed_max = float(t.item())
         elapsed_min = float(tmin.item())
+    if args.dump_outputs:  # (before any leg of --full moves the state on)
+        dump_outputs(sim, args.dump_outputs, rank, world)
     remesh_leg = None
-    if args.workload == "disk_amr" and not args.no_remesh_leg and world == 1 and not args.loopback:  # (the legs pick leaves by local index: one rank)
+    if (args.full and args.workload == "disk_amr" and not args.no_remesh_leg and world == 1
+            and not args.loopback):  # (the legs pick leaves by local index: one rank)
         # The remesh machinery on THIS mesh, outside the timed region: five leaves below the finest level, spread over
         # the Z-ordered list, are split one after the other as if the criterion had tagged them (2:1 balance, new
         # state, hand-over, tables), one cycle in between.  The disk is in equilibrium, so the deck's own criterion
@@ -615,15 +684,15 @@ def main():
             "what": "28 cycles after the timed region; five batches of injected +1 tags, the merges the criterion orders five "
                     "cycles after each"}
     kms, nlaunch = 0.0, 0
-    if args.workload not in ("disk_sph_smr", "disk_amr"):  # (refined meshes: whole-stage accounting below)
+    if args.full and args.workload not in ("disk_sph_smr", "disk_amr"):  # (refined meshes: whole-stage accounting below)
         sim.set_kernel_timing(True)   # HIP events around the dominant kernel, on the stream it is launched on
         sim.evolve(max(5, min(args.steps, 40)))
         kms, nlaunch = sim.kernel_ms()
         sim.set_kernel_timing(False)
-    hist = sim.history()
+    hist = sim.history() if args.full else None  # (a host-side sum over every zone: a check, not the headline)
     overlap_emulation = None
-    if (args.workload == "sedov3d" and args.gpus == 1 and not args.loopback and not args.no_overlap_emulation and sim.uses_tuned_kernel
-            and args.blocks_per_gpu == 1 and not force_overlap):
+    if (args.full and args.workload == "sedov3d" and args.gpus == 1 and not args.loopback and not args.no_overlap_emulation
+            and sim.uses_tuned_kernel and args.blocks_per_gpu == 1 and not force_overlap):
         # What a rank of an N > 1 run does per stage, emulated on this one GPU: the same zones as two blocks stacked along
         # x3 with the shell-first / bulk launch order forced (ARTEMIS_FORCE_OVERLAP: the boundary shell of every block is
         # launched first and its slabs are packed on the comm stream while the bulk runs; the "link" is a device copy).
@@ -642,7 +711,8 @@ def main():
         finally:
             L.artemis_hip_set_option(b"force_overlap", 0)
     dropin = None
-    if args.workload == "sedov3d" and args.gpus == 1 and not args.loopback and not args.no_dropin and sim.uses_tuned_kernel:
+    if (args.full and args.workload == "sedov3d" and args.gpus == 1 and not args.loopback and not args.no_dropin
+            and sim.uses_tuned_kernel):
         # What a Parthenon host sees: (i) the fused kernel also writing `cons` on the last
         # stage + the whole-block PrimToCons (FillDerived) after every stage's boundary fill; (ii) the
         # per-task chain of INTEGRATION.md section 2.  Same deck, same state, outside the timed region.
@@ -719,9 +789,10 @@ def main():
                               if getattr(comm, "fallback", None) else
                               "native C++ RCCL (ncclSend/ncclRecv groups per stage, ncclAllReduce(min) on the device dt); "
                               "ncclCommCount = %d rank(s)" % rccl_ranks),
-                "total_energy_check": float(hist[4]),
             },
         }
+        if hist is not None:
+            out["config"]["total_energy_check"] = float(hist[4])
         if overlap_emulation is not None:
             out["config"]["overlap_emulation_zcps"] = overlap_emulation
             out["config"]["overlap_emulation"] = ("the same zones as two blocks stacked along x3, shell-first + bulk launches forced "
@@ -858,9 +929,9 @@ def main():
                 dropin["fused"] = value
                 dropin["frac_fused"] = value * 2.0 * ALG_BYTES_PER_CELL_STAGE / 1.0e9 / HBM_PEAK_GBS
                 out["dropin"] = dropin
-        if args.workload == "linwave3d":
-            pass  # (a gap measurement: no CPU leg)
-        elif args.workload in ("disk_sph", "disk_sph_smr", "disk_amr") and not args.no_cpu_baseline:
+        if args.workload == "linwave3d" or not args.full or args.no_cpu_baseline:
+            pass  # (linwave3d is a gap measurement: no CPU leg)
+        elif args.workload in ("disk_sph", "disk_sph_smr", "disk_amr"):
             hc = host_cores()
             threads = args.cpu_threads or hc["physical_usable"]
             kind = "cyl_dust" if args.workload == "disk_amr" else "sph"
@@ -871,9 +942,7 @@ def main():
                           "(uniform mesh), %d cycles in %.1f s"
                           % (threads, "the cylindrical disk + planet + dust + drag + viscosity of configs[4]" if kind == "cyl_dust"
                              else "inputs/disk/disk_sph.in", cnx[0], cnx[1], cnx[2], cyc, secs)}
-        elif args.workload in ("disk_sph", "disk_sph_smr", "disk_amr"):
-            pass
-        elif args.workload == "ssheet_dust" and not args.no_cpu_baseline:
+        elif args.workload == "ssheet_dust":
             hc = host_cores()
             threads = args.cpu_threads or hc["physical_usable"]
             v, secs, cyc, cn = cpu_baseline_ssheet(min(args.n, 512), args.dust, args.cpu_cycles, threads)
@@ -882,7 +951,7 @@ def main():
                 "sample": "CPU oracle (C++ restatement of the reference's CPU path, OpenMP over rows) on %d threads (the "
                           "container's CPU quota, else one per physical core), same problem at %d^2, %d cycles, %.1f s"
                           % (threads, cn, cyc, secs)}
-        elif args.gpus == 1 and not args.no_cpu_baseline:
+        elif args.gpus == 1:
             hc = host_cores()
             threads = args.cpu_threads or hc["physical_usable"]
             v, secs, cyc = cpu_baseline(args.cpu_n, args.cpu_cycles, threads)

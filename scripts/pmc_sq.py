@@ -4,6 +4,7 @@ Runs `rocprofv3 --pmc <group> --kernel-trace` once per counter group (never with
 per-kernel means for kernels whose name contains 'stage' (or one of the comma-separated PMC_SQ_KERNELS)."""
 import collections, csv, glob, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, os.environ.get("JOB_OUT", "job_out"))  # (profiles and records)
 
 
 def library_identity(scope):
@@ -27,7 +28,7 @@ tag = sys.argv[1]
 prog = sys.argv[sys.argv.index("--") + 1:]
 acc = collections.defaultdict(dict)
 for gi, g in enumerate(GROUPS):
-    out = os.path.join(ROOT, "gpurun_out", "sq_%s_%d" % (tag, gi))
+    out = os.path.join(OUT, "sq_%s_%d" % (tag, gi))
     os.makedirs(out, exist_ok=True)
     cmd = ["rocprofv3", "--pmc"] + g + ["--kernel-trace", "--output-format", "csv", "-d", out, "-o", "p", "--", "python3"] + prog
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -48,7 +49,7 @@ for gi, g in enumerate(GROUPS):
             acc[k][c] = v / max(cnt[k], 1)
         acc[k]["launches"] = cnt[k]
 res = {k[:150]: v for k, v in acc.items()}
-json.dump(res, open(os.path.join(ROOT, "gpurun_out", "sq_%s.json" % tag), "w"), indent=1)
+json.dump(res, open(os.path.join(OUT, "sq_%s.json" % tag), "w"), indent=1)
 if os.environ.get("PMC_SQ_RECORD"):
     # the record bench.py quotes as roofline.fp64_issue (only while the kernel sources are unchanged): mean VALU
     # wave-instructions per launch over the headline stage kernels (non-curvilinear, non-flux instantiations)
@@ -60,7 +61,7 @@ if os.environ.get("PMC_SQ_RECORD"):
                "valu_active_cycles": sum(v.get("SQ_ACTIVE_INST_VALU", 0.0) for v in ks.values()) / len(ks),
                "wave_cycles": sum(v.get("SQ_WAVE_CYCLES", 0.0) for v in ks.values()) / len(ks),
                "kernels": sorted(ks)}
-        json.dump(rec, open(os.path.join(ROOT, "gpurun_out", "%s_pmc_sq.json" % os.environ["PMC_SQ_RECORD"]), "w"), indent=1)
+        json.dump(rec, open(os.path.join(OUT, "%s_pmc_sq.json" % os.environ["PMC_SQ_RECORD"]), "w"), indent=1)
 for k, v in res.items():
     print(k[:120])
     print("   ", {c: round(x, 1) for c, x in v.items()})

@@ -2,11 +2,13 @@
 """Measure the HBM traffic of the dominant kernel with rocprofv3 PMC counters and write the record
 bench.py quotes as `roofline.traffic`.
 
-    gpurun -- python3 scripts/pmc_traffic.py [--tag r02] [--workload sedov3d|disk_sph|ssheet_dust] [bench args]
+    python3 scripts/pmc_traffic.py [--tag r02] [--workload sedov3d|disk_sph|ssheet_dust] [bench args]
+
+(on a GPU machine; records and profiles go under $JOB_OUT, default job_out/)
 
 Separate `rocprofv3 --pmc` passes (FETCH_SIZE needs 3 of the 4 TCC slots, WRITE_SIZE 2:
 MI355X_MICROARCH.md "rocprofv3 PMC slots"; nothing but --kernel-trace next to --pmc).  Sedov: two passes of
-`python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-overlap-emulation`, whose `dropin` legs also run the
+`python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-overlap-emulation`, whose `dropin` legs also run the
 per-task kernels (the calibration), and two of the same command with `--no-dropin` as well -- every stage launch of
 that run is a full-size launch of one of the two headline instantiations, their number is known (2 x (warmup + steps +
 the kernel-timing leg's cycles)) and the record is refused by bench.py if the profile holds any other count.  The calibration: gfx950's FETCH_SIZE under-reports coalesced streams (exactly 1/2
@@ -27,6 +29,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, os.environ.get("JOB_OUT", "job_out"))
 
 
 def library_identity(scope):
@@ -75,7 +78,7 @@ def whole_stage(args, extra):
     refined = args.workload in ("disk_amr", "disk_sph_smr")
 
     def bench_args_for(steps):
-        a = ["--workload", args.workload, "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline"] + (["--n", str(n)] if n else []) + extra
+        a = ["--full", "--workload", args.workload, "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline"] + (["--n", str(n)] if n else []) + extra
         if args.workload == "disk_amr":  # (stages only: the remesh measurements that follow the timed region are left out)
             a.append("--no-remesh-leg")
         return a
@@ -101,7 +104,7 @@ def whole_stage(args, extra):
 
     def measure(steps, tagx):
         bench_args = bench_args_for(steps)
-        scratch = os.path.join(ROOT, "gpurun_out", "pmc_%s%s" % (args.tag, tagx))
+        scratch = os.path.join(OUT, "pmc_%s%s" % (args.tag, tagx))
         fetch = run_pass("FETCH_SIZE", scratch + "_fetch", bench_args)
         write = run_pass("WRITE_SIZE", scratch + "_write", bench_args)
         kernels = {}
@@ -142,7 +145,7 @@ def whole_stage(args, extra):
         "fetch_correction": "true_read = FETCH_SIZE / %.4f (calibration of %s)" % (ratio, src),
         "stages": nstage, "kernels": kernels, "hbm_bytes_per_launch": per_stage,
     }
-    out = args.out or os.path.join(ROOT, "gpurun_out", "%s_%s_pmc_traffic.json" % (args.tag, ("cfg3" if n == 4096 else "cfg3_%d" % n) if args.workload == "ssheet_dust" else args.workload))
+    out = args.out or os.path.join(OUT, "%s_%s_pmc_traffic.json" % (args.tag, ("cfg3" if n == 4096 else "cfg3_%d" % n) if args.workload == "ssheet_dust" else args.workload))
     rec["n"] = n
     json.dump(rec, open(out, "w"), indent=1)
     print(json.dumps({"hbm_bytes_per_stage": per_stage, "stages": nstage, "out": out}))
@@ -159,8 +162,8 @@ def main():
     if args.workload != "sedov3d":
         return whole_stage(args, extra)
     steps, warmup = 6, 2
-    bench_args = ["--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-overlap-emulation", "--n", str(args.n)] + extra
-    scratch = os.path.join(ROOT, "gpurun_out", "pmc_%s" % args.tag)
+    bench_args = ["--full", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-overlap-emulation", "--n", str(args.n)] + extra
+    scratch = os.path.join(OUT, "pmc_%s" % args.tag)
     fetch = run_pass("FETCH_SIZE", scratch + "_fetch", bench_args)   # with the dropin legs: the calibration kernels
     write = run_pass("WRITE_SIZE", scratch + "_write", bench_args)
     head_args = bench_args + ["--no-dropin"]                         # the headline path alone: full-size launches only
@@ -214,7 +217,7 @@ def main():
         "headline_command": "python3 bench.py " + " ".join(head_args),
         "algorithmic_bytes_per_launch": ALG_BYTES_PER_CELL_STAGE * interior,
     }
-    out = args.out or os.path.join(ROOT, "gpurun_out", "%s_pmc_traffic.json" % args.tag)
+    out = args.out or os.path.join(OUT, "%s_pmc_traffic.json" % args.tag)
     json.dump(rec, open(out, "w"), indent=1)
     print(json.dumps({"hbm_bytes_per_launch": per_launch, "fetch_ratio": ratio, "write_ratio": wratio, "out": out}))
 
