@@ -900,6 +900,7 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
   if (!a) return fail(ARTEMIS_HIP_EINVAL, "null stage args");
   if (int rc = validate_fluid(p, ARTEMIS_GAS, a->pcm)) return rc;
   if (int rc = validate_fluid(p, ARTEMIS_DUST, a->pcm)) return rc;
+  if (a->defer_finish < 0 || a->defer_finish > 2) return fail(ARTEMIS_HIP_EINVAL, "general stage: defer_finish must be 0, 1 or 2");
   if (p->gas.nspecies && (!a->gas_in || !a->gas_u1 || !a->gas_out))
     return fail(ARTEMIS_HIP_EINVAL, "general stage: gas_in / gas_u1 / gas_out are required");
   if (p->dust.nspecies && (!a->dust_in || !a->dust_u1 || !a->dust_out))
@@ -954,6 +955,7 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
 
 int artemis_hip_stage_general_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a) {
   if (!p || !a) return 0;
+  if (a->defer_finish < 0 || a->defer_finish > 2) return 0; // (artemis_hip_stage_general refuses such a call: EINVAL)
   return artemis::stage_general_variant(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon,
                                         p->dust.riemann);
 }

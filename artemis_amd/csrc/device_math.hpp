@@ -119,6 +119,28 @@ ADEV void ppm4(double qmm, double qm, double q, double qp, double qpp, double &q
   qlp = qrv;
   qr = qlv;
 }
+// same face values with the two divisions by 12 through one shared refined reciprocal, r12 = recip(12.0) formed once by
+// the caller (the PPM tile march, kernels_ppm.hip).  `div` gives the bits of `/` while the numerator is zero or a
+// normal number of at least 2^-969: callers pass through here only where no tiny-but-nonzero value is in the stencil.
+ADEV void ppm4_fast(double qmm, double qm, double q, double qp, double qpp, const Recip &r12, double &qlp, double &qr) {
+  double qlv = div(7. * (q + qm) - (qmm + qp), r12);
+  double qrv = div(7. * (q + qp) - (qm + qpp), r12);
+  qlv = amax(qlv, amin(q, qm));
+  qlv = amin(qlv, amax(q, qm));
+  qrv = amax(qrv, amin(q, qp));
+  qrv = amin(qrv, amax(q, qp));
+  const double qc = qrv - q;
+  const double qd = qlv - q;
+  if ((qc * qd) >= 0.0) {
+    qlv = q;
+    qrv = q;
+  } else {
+    if (fabs(qc) >= 2.0 * fabs(qd)) qrv = q - 2.0 * qd;
+    if (fabs(qd) >= 2.0 * fabs(qc)) qlv = q - 2.0 * qc;
+  }
+  qlp = qrv;
+  qr = qlv;
+}
 
 // RECON: 0 pcm (pcm.hpp:34-88), 1 plm, 2 ppm.  `w` points at the cell, `st` = stride of the
 // sweep direction.  Outputs the cell's two face values: upper (= ql of face+1) and lower

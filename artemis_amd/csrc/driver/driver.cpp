@@ -3808,12 +3808,14 @@ const char *artemis_sim_stage_kernel(const artemis_sim_t *s) {
   if (s->p->multilevel && s->p->ml_fused) {
     if (s->p->ml_tuned) return "stage_fused_kernel + coarse-fine fix-up";
     if (s->p->general_variant == 3) return "stage_curv_kernel + coarse-fine fix-up";
+    if (s->p->general_variant == 4) return "stage_ppm_kernel + coarse-fine fix-up";
     return s->p->general_variant == 2 ? "stage_fused_kernel<curvilinear> + coarse-fine fix-up" : "stage_cell_kernel + coarse-fine fix-up";
   }
   if (!s->p->use_fused) return "per-task chain";
   if (s->p->tuned) return "stage_fused_kernel";
   if (s->p->general_variant < 0) return "general stage (not run yet)";
   if (s->p->general_variant == 3) return "stage_curv_kernel";
+  if (s->p->general_variant == 4) return "stage_ppm_kernel";
   return s->p->general_variant == 1 ? "stage2d_kernel" : (s->p->general_variant == 2 ? "stage_fused_kernel<curvilinear>" : "stage_cell_kernel");
 }
 long artemis_sim_remeshes(const artemis_sim_t *s) { return s->remeshes; }

@@ -51,6 +51,20 @@ ADEV int opaque(int i) {
   return i;
 }
 
+// Neighbour exchange inside the wave with DPP wave shifts (one VALU move per dword, no LDS crossbar, no
+// lgkmcnt wait): lane i reads lane i - 1 (wave_shr:1) or lane i + 1 (wave_shl:1); the wave's end lanes keep
+// their own value (callers overwrite or never use what those lanes get).
+ADEV double lane_below(double v) { // the value held by lane - 1
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false),
+                          __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));
+}
+ADEV double lane_above(double v) { // the value held by lane + 1
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false),
+                          __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false));
+}
+
 template <class IDX>
 ADEV Cell6 load_cell(const double *__restrict__ r, const double *__restrict__ v1,
                      const double *__restrict__ v2, const double *__restrict__ v3,

@@ -75,6 +75,9 @@ bool curv_march_covers_dust(const PackView &P, const artemis_stage_general_args_
 // left its conserved state in P.gas.cons0) and, with g.dt_dev, both fluids' timestep limits
 void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g, int fluid, int recon, int riemann, hipStream_t s,
                        bool finish = false);
+// kernels_ppm.hip: the PPM tile march (Cartesian 3-D, one gas species; ppm_march_covers in kernels_stage_cell.hip)
+bool ppm_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas);
+void launch_stage_ppm(const PackView &P, const artemis_stage_general_args_t &g, int riemann, hipStream_t s);
 // kernels_diffusion.hip
 void launch_zero_diffusion_flux(const PackView &P, hipStream_t s);
 // overwrite: ZeroDiffusionFlux folded in (the flux arrays are overwritten on the face ranges)

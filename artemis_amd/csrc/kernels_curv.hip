@@ -188,17 +188,7 @@ ADEV Flux8 solve_fluid(const GasK &gk, const Cell6 &L, const Cell6 &R, const boo
   if constexpr (!DUST)                                                                     \
   fl.e = A[4] __VA_ARGS__, fl.eg = A[5] __VA_ARGS__, fl.pf = A[6] __VA_ARGS__, fl.vf = A[7] __VA_ARGS__
 
-// the value held by the lane below / above (kernels_stage2d.hip: wave_shr:1 / wave_shl:1, one move per dword)
-ADEV double lane_below(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));
-}
-ADEV double lane_above(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false));
-}
+// (x1 neighbours: lane_below / lane_above, fused_device.hpp)
 
 // Workgroup `id` of the launch: tile (ti, tj), chunk and block (ids dealt so that each XCD's L2 sees one run of tiles)
 // EXT: the instantiations that stop at the conserved state (drag follows) and / or carry N-body gravity

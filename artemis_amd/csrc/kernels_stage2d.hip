@@ -70,20 +70,7 @@ struct DFlux {
   double d, m1, m2, m3;
 };
 
-// Neighbour exchange inside the wave with DPP wave shifts (one VALU move per dword, no LDS crossbar, no
-// lgkmcnt wait): lane i reads lane i - 1 (wave_shr:1) or lane i + 1 (wave_shl:1); the wave's end lanes keep
-// their own value (they are halo lanes whose results are never used).
-ADEV double lane_below(double v) { // the value held by lane - 1
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));
-}
-ADEV double lane_above(double v) { // the value held by lane + 1
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false));
-}
-
+// (neighbour exchange inside the wave: lane_below / lane_above, fused_device.hpp)
 template <class IDX>
 ADEV Dust4 load_dust(const double *r, const double *v1, const double *v2, const double *v3, IDX c) {
   Dust4 q;

@@ -1,6 +1,7 @@
 // Cell-centred fused stage: the general one-kernel-per-fluid form of the reference's stage
 // (artemis_driver.cpp:182-255) for everything the tuned gas kernel (kernels_fused.hip) does not
 // cover -- dust, several species, PPM, curvilinear coordinates, gravity / rotating-frame / drag.
+// (One gas species with PPM on Cartesian 3-D blocks has a tile march of its own since: kernels_ppm.hip, variant 4.)
 //
 // One thread owns one cell.  For each species it computes the 2*ndim face fluxes of its own cell
 // straight from the input primitives (each face is therefore solved by both cells that share
@@ -640,8 +641,22 @@ void launch_stage_epilogue(const PackView &P, const artemis_stage_general_args_t
   }
 }
 
+// What the PPM tile march (kernels_ppm.hip, variant 4) takes: one gas species alone on Cartesian 3-D blocks, PPM4 with
+// its three ghost zones, every ghost zone filled by the caller, none of the optional tasks.  Everything else -- PPM
+// packs with dust, the PCM predictor stage of vl2, 1-D / 2-D, curvilinear systems, refined meshes (defer_finish != 0)
+// -- keeps the variant it had.
+bool ppm_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas) {
+  if (P.coords != ARTEMIS_CARTESIAN || P.ndim != 3) return false;
+  if (P.gas.ns != 1 || P.dust.ns != 0) return false;
+  if (g.pcm || recon_gas != ARTEMIS_PPM || P.ng < 3) return false;
+  if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false; // (32-bit element offsets)
+  if (g.gravity || g.rf_omega != 0.0 || g.drag || g.diffusion || g.cooling || g.nbody_n) return false;
+  return g.defer_finish == 0 && g.strat_faces == 0;
+}
+
 int stage_general_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
                           int recon_dust, int riemann_dust) {
+  if (!opt(OPT_NO_PPM_MARCH) && ppm_march_covers(P, g, recon_gas)) return 4;
   if (!opt(OPT_NO_STAGE2D) && stage2d_covers(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust)) return 1;
   if (!opt(OPT_NO_FUSED_CURV)) {
     if (curv_march_covers(P, g, recon_gas)) return 3;
@@ -657,6 +672,10 @@ void launch_stage_cell(const PackView &P, const artemis_stage_general_args_t &g,
   const int variant = stage_general_variant(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust);
   if (variant == 1) {
     launch_stage2d(P, g, recon_gas, riemann_gas, riemann_dust, s);
+    return;
+  }
+  if (variant == 4) { // Cartesian 3-D gas with PPM: the whole stage and its timestep limit on the tile march (kernels_ppm.hip)
+    launch_stage_ppm(P, g, riemann_gas, s);
     return;
   }
   if (variant == 2) { // curvilinear gas with diffusion from stored flux arrays: the older march, geometry in registers

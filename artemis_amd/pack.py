@@ -223,7 +223,7 @@ class MeshBlockPack:
             a.nbody_dev, a.nbody_n, a.nbody_omf = nbody[0].data_ptr(), nbody[1], nbody_omf
         a.defer_finish = int(defer_finish)  # (False / True, or the ABI's 0 / 1 / 2)
         self._last_general_args = a
-        # which kernel this call takes (0 cell-centred, 1 2-D row march, 2 curvilinear streaming tile)
+        # which kernel this call takes (0 cell-centred, 1 2-D row march, 2 / 3 curvilinear streaming tile, 4 PPM tile march)
         self.last_stage_variant = self.L.artemis_hip_stage_general_variant(C.byref(self.pack), C.byref(a))
         self._call(self.L.artemis_hip_stage_general, C.byref(a))
 

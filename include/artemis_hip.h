@@ -43,7 +43,8 @@
  *    NO_TUNED, TUNED_2D, NO_STAGE2D, NO_FUSED_CURV, NO_CURV_MARCH, NO_CURV_DUST, NO_CURV_DUST_MARCH, NO_DRAG_IN_MARCH
  *    (the drag finish as its own launch instead of inside the dust march), NO_STRAT_IN_KERNEL (the `strat` conditions as
  *    boundary-fill launches instead of inside the 2-D row march), NO_CART_MARCH (Cartesian packs with gravity / viscosity on
- *    the cell-centred stage instead of the tile march of kernels_curv.hip), NO_IC_IN_SHELL (`ic` faces as their own
+ *    the cell-centred stage instead of the tile march of kernels_curv.hip), NO_PPM_MARCH (one gas species with PPM on
+ *    Cartesian 3-D blocks on the cell-centred stage instead of the PPM tile march of kernels_ppm.hip), NO_IC_IN_SHELL (`ic` faces as their own
  *    boundary-fill launches instead of inside the one-launch fill of the copy-type conditions), NO_IC_SKIP (host driver, refined
  *    meshes: `ic` faces refilled at every ghost fill although their zones never change), NO_ML_FUSED,
  *    NO_EPILOGUE, NO_TILED_FLUX, NO_VISC_SOURCE (the diffusion-flux tasks instead of artemis_hip_viscous_source),
@@ -631,7 +632,12 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
  * (kernels_stage2d.hip: both fluids, drag, aux, ConsToPrim and dt in one launch), 3 = the curvilinear tile march
  * (kernels_curv.hip: gas on any non-Cartesian system, geometry in LDS tables, two waves per SIMD; diffusion only as
  * diffusion_sums), 2 = its predecessor with the geometry in registers (kernels_fused.hip: taken when the diffusion
- * fluxes come from stored arrays).  Same results either way; benchmarks name the kernel they timed with this. */
+ * fluxes come from stored arrays), 4 = the PPM tile march (kernels_ppm.hip: one gas species alone on Cartesian 3-D
+ * blocks, gas.recon = PPM and pcm = 0, nghost >= 3, none of the optional tasks -- gravity, rotating frame, drag,
+ * diffusion, cooling, N-body, strat_faces -- and defer_finish = 0; any block extents, any number of blocks, gas_u1 equal
+ * to gas_in or not, dt_dev set or not.  PPM packs with dust, the PCM predictor stage of vl2 (pcm = 1), 1-D / 2-D
+ * blocks and curvilinear systems keep the variant they had).  Same results either way; benchmarks name the kernel they
+ * timed with this.  A defer_finish outside 0 .. 2 gives 0 here and ARTEMIS_HIP_EINVAL from artemis_hip_stage_general. */
 int artemis_hip_stage_general_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a);
 /* The cell-local remainder of a stage in ONE pass over stored fluxes: after Gas/Dust::CalculateFluxes
  * (and the diffusion-flux tasks) have filled flux / pflux / vface (/ diff_flux) for p's primitives,
