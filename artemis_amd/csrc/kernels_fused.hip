@@ -254,13 +254,14 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   FPROF(0);
   constexpr bool PG = CURV && RECON == 1; // PLM_G instead of the uniform-mesh slope
   bool fastp = true; // every division hand-scheduled (no tiny velocity in this plane's tile)
-  if constexpr (GUARD || DETECT) {
-    if (GUARD || det) { // (det: wave-uniform, the stage's input may hold a tiny velocity at all)
-      flagged = (tiny_flag(S, k & 1) != 0);
-      if constexpr (GUARD) fastp = !flagged;
-      if (x.t == 0) tiny_flag(S, (k + 1) & 1) = 0; // set again when the next plane is staged (after the barrier)
-    }
-  }
+  // LDS ordering rule of this function (pattern 5): a store to S orders every later load of S
+  // behind it -- the compiler cannot tell the members apart through run-time indices -- and a load that is used at
+  // once exposes its whole round trip.  So every phase REQUESTS all it reads first, computes, and stores last.
+  // The plane flag is requested with the plane's first reads and waited for where it is used.  (No branch around the
+  // read -- the compiler would finish it inside: a stage that does not detect never sets a flag and reads the 0 the
+  // kernel's prologue stored.)
+  [[maybe_unused]] int flag_ = 0;
+  if constexpr (GUARD || DETECT) flag_ = tiny_flag(S, k & 1);
   const int tx = x.tx, ty = x.ty;
   const bool multi_d = D3 || x.multi_d; // compile-time true in the 3-D instantiation
   const int t = (x.t + 64 * (k % NW)) % NT; // duty index: wave roles rotate with k
@@ -276,97 +277,105 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
 #endif
   // ---- P1: slopes of the own cell; perimeter slopes on waves 2 (x1) and 3 (x2) -----------
   Cell6 lox, loy;
-#define SLX(m, n)                                                                          \
-  {                                                                                        \
-    double up_, lo_;                                                                       \
-    if constexpr (PG) {                                                                    \
-      if (fastp)                                                                           \
-        plm_g_shared<2>(S.Q[n][ty + FH][tx + FH - 1], qc.m, S.Q[n][ty + FH][tx + FH + 1],  \
-                        up_, lo_, gx.g1);                                                  \
-      else                                                                                 \
-        plm_g_shared<0>(S.Q[n][ty + FH][tx + FH - 1], qc.m, S.Q[n][ty + FH][tx + FH + 1],  \
-                        up_, lo_, gx.g1);                                                  \
-    } else {                                                                               \
-      const double s_ =                                                                    \
-          slope_sel<RECON>(S.Q[n][ty + FH][tx + FH - 1], qc.m, S.Q[n][ty + FH][tx + FH + 1], fastp);  \
-      lo_ = lo_val<RECON>(qc.m, s_), up_ = up_val<RECON>(qc.m, s_);                        \
-    }                                                                                      \
-    lox.m = lo_;                                                                           \
-    S.UPX[n][ty][tx + 1] = up_;                                                            \
-  }
-  SLX(d, 0) SLX(v1, 1) SLX(v2, 2) SLX(v3, 3) SLX(p, 4) SLX(e, 5)
-#undef SLX
+  double xm_[6], xp_[6], ym_[6], yp_[6]; // the own cell's neighbours of both directions: 24 reads in flight at once
+#pragma unroll
+  for (int n = 0; n < 6; ++n) xm_[n] = S.Q[n][ty + FH][tx + FH - 1], xp_[n] = S.Q[n][ty + FH][tx + FH + 1];
   if (multi_d) {
-#define SLY(m, n)                                                                          \
+#pragma unroll
+    for (int n = 0; n < 6; ++n) ym_[n] = S.Q[n][ty + FH - 1][tx + FH], yp_[n] = S.Q[n][ty + FH + 1][tx + FH];
+  }
+  if constexpr (GUARD) flagged = (flag_ != 0), fastp = !flagged;
+  double ux_[6], uy_[6]; // upper face values: stored after the last slope
+#define SLOPE(m, n, lm, rm, lov, upv, geo)                                                 \
   {                                                                                        \
     double up_, lo_;                                                                       \
     if constexpr (PG) {                                                                    \
-      if (fastp)                                                                           \
-        plm_g_shared<2>(S.Q[n][ty + FH - 1][tx + FH], qc.m, S.Q[n][ty + FH + 1][tx + FH],  \
-                        up_, lo_, gx.g2);                                                  \
-      else                                                                                 \
-        plm_g_shared<0>(S.Q[n][ty + FH - 1][tx + FH], qc.m, S.Q[n][ty + FH + 1][tx + FH],  \
-                        up_, lo_, gx.g2);                                                  \
+      if (fastp) plm_g_shared<2>(lm[n], qc.m, rm[n], up_, lo_, geo);                       \
+      else plm_g_shared<0>(lm[n], qc.m, rm[n], up_, lo_, geo);                             \
     } else {                                                                               \
-      const double s_ =                                                                    \
-          slope_sel<RECON>(S.Q[n][ty + FH - 1][tx + FH], qc.m, S.Q[n][ty + FH + 1][tx + FH], fastp);  \
+      const double s_ = slope_sel<RECON>(lm[n], qc.m, rm[n], fastp);                       \
       lo_ = lo_val<RECON>(qc.m, s_), up_ = up_val<RECON>(qc.m, s_);                        \
     }                                                                                      \
-    loy.m = lo_;                                                                           \
-    S.UPY[n][ty + 1][tx] = up_;                                                            \
+    lov.m = lo_;                                                                           \
+    upv[n] = up_;                                                                          \
   }
-    SLY(d, 0) SLY(v1, 1) SLY(v2, 2) SLY(v3, 3) SLY(p, 4) SLY(e, 5)
+#define SLX(m, n) SLOPE(m, n, xm_, xp_, lox, ux_, gx.g1)
+#define SLY(m, n) SLOPE(m, n, ym_, yp_, loy, uy_, gx.g2)
+  SLX(d, 0) SLX(v1, 1) SLX(v2, 2) SLX(v3, 3) SLX(p, 4) SLX(e, 5)
+  if (multi_d) { SLY(d, 0) SLY(v1, 1) SLY(v2, 2) SLY(v3, 3) SLY(p, 4) SLY(e, 5) }
+#undef SLX
 #undef SLY
+#undef SLOPE
+#pragma unroll
+  for (int n = 0; n < 6; ++n) S.UPX[n][ty][tx + 1] = ux_[n];
+  if (multi_d) {
+#pragma unroll
+    for (int n = 0; n < 6; ++n) S.UPY[n][ty + 1][tx] = uy_[n];
+  }
+  if constexpr (GUARD || DETECT) { // set again when the next plane is staged (after the barrier); behind the reads above
+    if ((GUARD || det) && x.t == 0) tiny_flag(S, (k + 1) & 1) = 0;
+  }
+  // A perimeter duty: the six slopes of one cell outside the tile.  Its 18 values are requested before the first slope and
+  // its six face values stored after the last (`geo`: the cell's PLM_G record, read only by the curvilinear kernel).
+#define DUTY_SLOPES(geo)                                                                   \
+  _Pragma("unroll") for (int n = 0; n < 6; ++n) {                                          \
+    double up_, lo_;                                                                       \
+    if constexpr (PG) {                                                                    \
+      if (fastp) plm_g_shared<2>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                   \
+      else plm_g_shared<0>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                         \
+    } else {                                                                               \
+      const double s_ = slope_sel<RECON>(pm_[n], pc_[n], pp_[n], fastp);                   \
+      lo_ = lo_val<RECON>(pc_[n], s_), up_ = up_val<RECON>(pc_[n], s_);                    \
+    }                                                                                      \
+    po_[n] = side ? lo_ : up_;                                                             \
   }
   if (t >= 128 && t < 128 + 2 * FTY) { // cells i0-1 (upper value) and i0+32 (lower value)
     const int u = t - 128, row = u >> 1, side = u & 1;
     const int cx = side ? FTX + FH : FH - 1;
+    double pm_[6], pc_[6], pp_[6], po_[6];
+#pragma unroll
+    for (int n = 0; n < 6; ++n)
+      pm_[n] = S.Q[n][row + FH][cx - 1], pc_[n] = S.Q[n][row + FH][cx], pp_[n] = S.Q[n][row + FH][cx + 1];
+    DUTY_SLOPES(S.GX1[side])
 #pragma unroll
     for (int n = 0; n < 6; ++n) {
-      const double q = S.Q[n][row + FH][cx];
-      double up_, lo_;
-      if constexpr (PG) {
-        if (fastp) plm_g_shared<2>(S.Q[n][row + FH][cx - 1], q, S.Q[n][row + FH][cx + 1], up_, lo_, S.GX1[side]);
-        else plm_g_shared<0>(S.Q[n][row + FH][cx - 1], q, S.Q[n][row + FH][cx + 1], up_, lo_, S.GX1[side]);
-      } else {
-        const double s_ = slope_sel<RECON>(S.Q[n][row + FH][cx - 1], q, S.Q[n][row + FH][cx + 1], fastp);
-        lo_ = lo_val<RECON>(q, s_), up_ = up_val<RECON>(q, s_);
-      }
-      if (side) S.LOX[n][row] = lo_;
-      else S.UPX[n][row][0] = up_;
+      if (side) S.LOX[n][row] = po_[n];
+      else S.UPX[n][row][0] = po_[n];
     }
   }
   if (multi_d && t >= 192 && t < 256) { // rows j0-1 (upper value) and j0+8 (lower value)
     const int u = t - 192, cx = u & 31, side = u >> 5;
     const int ry = side ? FTY + FH : FH - 1;
+    double pm_[6], pc_[6], pp_[6], po_[6];
+#pragma unroll
+    for (int n = 0; n < 6; ++n)
+      pm_[n] = S.Q[n][ry - 1][cx + FH], pc_[n] = S.Q[n][ry][cx + FH], pp_[n] = S.Q[n][ry + 1][cx + FH];
+    DUTY_SLOPES(S.GX2[side][cx])
 #pragma unroll
     for (int n = 0; n < 6; ++n) {
-      const double q = S.Q[n][ry][cx + FH];
-      double up_, lo_;
-      if constexpr (PG) {
-        if (fastp) plm_g_shared<2>(S.Q[n][ry - 1][cx + FH], q, S.Q[n][ry + 1][cx + FH], up_, lo_, S.GX2[side][cx]);
-        else plm_g_shared<0>(S.Q[n][ry - 1][cx + FH], q, S.Q[n][ry + 1][cx + FH], up_, lo_, S.GX2[side][cx]);
-      } else {
-        const double s_ = slope_sel<RECON>(S.Q[n][ry - 1][cx + FH], q, S.Q[n][ry + 1][cx + FH], fastp);
-        lo_ = lo_val<RECON>(q, s_), up_ = up_val<RECON>(q, s_);
-      }
-      if (side) S.LOY[n][cx] = lo_;
-      else S.UPY[n][0][cx] = up_;
+      if (side) S.LOY[n][cx] = po_[n];
+      else S.UPY[n][0][cx] = po_[n];
     }
   }
+#undef DUTY_SLOPES
+  if constexpr (DETECT) flagged = (flag_ != 0); // (needed by plane_update only)
   FPROF(1);
   __syncthreads();
   FPROF(2);
   // ---- P2: Riemann problems at the own lower faces; perimeter faces on wave 1 ------------
-  Cell6 L;
+  // Both left states are requested before the first face is published.  The perimeter pass stays behind the wave's own
+  // solves and requests its states there: ahead of them it holds both left states through a third solver pass and the
+  // stage-2 kernels spill (48 - 64 bytes of scratch with all three of HLLC, HLLE, LLF).
+  Cell6 L, L2;
   GET6(L, S.UPX, [ty][tx]);
+  L2 = L;
+  if (multi_d) { GET6(L2, S.UPY, [ty][tx]); }
   fx_lo = solve_face<RIEMANN, 1>(x.gk, L, lox, fastp);
   if constexpr (CURV) fx_lo.m2 *= gx.h1[1], fx_lo.m3 *= gx.h1[2]; // ScaleMomentumFlux (h1 == 1)
   if (tx > 0) { PUT8(S.FX, fx_lo, [ty][tx - 1]); }
   fy_lo = fx_lo;
   if (multi_d) {
-    GET6(L, S.UPY, [ty][tx]);
-    fy_lo = solve_face<RIEMANN, 2>(x.gk, L, loy, fastp);
+    fy_lo = solve_face<RIEMANN, 2>(x.gk, L2, loy, fastp);
     if constexpr (CURV) fy_lo.m2 *= gx.h2[1], fy_lo.m3 *= gx.h2[2];
     if (ty > 0) { PUT8(S.FY, fy_lo, [ty - 1][tx]); }
   }

@@ -43,6 +43,13 @@ def library_identity(scope):
 
 
 
+def knob_env():
+    """The ARTEMIS_* knobs the profiled run was started with (bench.py quotes a record only if there were none).
+    ARTEMIS_NO_BUILD_CHECK is not one: it selects nothing in the library, it only skips the build check at load time --
+    what the skipped check would have guaranteed is what the record's `library_identity` states."""
+    return {k: v for k, v in os.environ.items() if k.startswith("ARTEMIS_") and k != "ARTEMIS_NO_BUILD_CHECK"}
+
+
 def run_pass(counter, outdir, bench_args):
     os.makedirs(outdir, exist_ok=True)
     cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", outdir, "-o", "p", "--",
@@ -141,7 +148,7 @@ def whole_stage(args, extra):
         "source": "scripts/pmc_traffic.py --workload %s: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, "
                   "--kernel-trace only) of `python3 bench.py %s`, MI355X; %s" % (args.workload, " ".join(bench_args), method),
         "workload": args.workload, "sha_scope": "all", "library_identity": library_identity("all"),
-        "env": {k: v for k, v in os.environ.items() if k.startswith("ARTEMIS_")},
+        "env": knob_env(),
         "fetch_correction": "true_read = FETCH_SIZE / %.4f (calibration of %s)" % (ratio, src),
         "stages": nstage, "kernels": kernels, "hbm_bytes_per_launch": per_stage,
     }
@@ -208,7 +215,7 @@ def main():
                   "of `python3 bench.py %s`, MI355X" % " ".join(bench_args),
         "units": "FETCH_SIZE / WRITE_SIZE are KiB per dispatch",
         "workload": "sedov3d", "sha_scope": "fused", "library_identity": library_identity("fused"),
-        "env": {k: v for k, v in os.environ.items() if k.startswith("ARTEMIS_")},
+        "env": knob_env(),
         "calibration": dict(calib, fetch_correction="true_read = FETCH_SIZE / %.4f (mean of the calibration kernels); "
                                                     "WRITE_SIZE as reported (calibrates at %.3f)" % (ratio, wratio)),
         "stage_fused_kernel": stage,
