@@ -99,6 +99,22 @@ ADEV double plm_dqm_fast(double qm, double q, double qp) {
   return (dq2 <= 0.0) ? 0.0 : dqm;
 }
 
+// plm_dqm_fast behind a wave-uniform guard (the Cartesian tile march): where the limiter zeroes the slope on every
+// active lane -- gas with no gradient along the sweep -- the quotient is not formed at all (one v_rcp_f64 and eight
+// fp64 instructions).  Otherwise the same expression tree and the same select: the same bits either way.  __all of
+// the comparison itself, not !__any of its negation: a NaN leaves `flat` false and takes the division as before.
+ADEV double plm_dqm_fast_skip(double qm, double q, double qp) {
+  const double dql = q - qm;
+  const double dqr = qp - q;
+  const double dq2 = dql * dqr;
+  const bool flat = (dq2 <= 0.0);
+  if (__all(flat)) return 0.0;
+  const double dqm = div(dq2, dql + dqr);
+  return flat ? 0.0 : dqm;
+}
+// The limiter's verdict alone, for callers that put several slopes behind one guard.
+ADEV bool plm_flat(double qm, double q, double qp) { return ((q - qm) * (qp - q)) <= 0.0; }
+
 // utils/fluxes/reconstruction/ppm.hpp:33-66 (PPM4).  Returns ql(i+1) in `qlp`, qr(i) in `qr`.
 ADEV void ppm4(double qmm, double qm, double q, double qp, double qpp, double &qlp, double &qr) {
   double qlv = (7. * (q + qm) - (qmm + qp)) / 12.0;
@@ -229,6 +245,62 @@ ADEV void hllc_gas_fast(const double gm1, const double igm1, const double gamma,
   const double pmid = 0.5 * (L.p + R.p + (L.vx - R.vx) * rc_avg);
   const double ql = (pmid <= L.p) ? 1.0 : sqrt_pos(1.0 + alpha * (div(pmid, L.p) - 1.0));
   const double qr = (pmid <= R.p) ? 1.0 : sqrt_pos(1.0 + alpha * (div(pmid, R.p) - 1.0));
+  const double sl = L.vx - cl * ql;
+  const double sr = R.vx + cr * qr;
+  const double bp = sr > 0.0 ? sr : 1.0e-20;
+  const double bm = sl < 0.0 ? sl : -1.0e-20;
+  const double vxl = L.vx - sl;
+  const double vxr = R.vx - sr;
+  const double tl = L.p + vxl * L.d * L.vx;
+  const double tr = R.p + vxr * R.d * R.vx;
+  const double ml = L.d * vxl;
+  const double mr = -(R.d * vxr);
+  const Recip rm = recip(ml + mr);
+  const double am = div(tl - tr, rm);
+  double cp = div(ml * tr + mr * tl, rm);
+  cp = cp > 0.0 ? cp : 0.0;
+  const double fld = L.d * (L.vx - bm);
+  const double frd = R.d * (R.vx - bp);
+  const double fle = el * (L.vx - bm) + L.p * L.vx;
+  const double fre = er * (R.vx - bp) + R.p * R.vx;
+  const bool pos = (am >= 0.0);
+  const Recip rw = recip(pos ? (am - bm) : (bp - am));
+  const double wa = div(pos ? am : -am, rw);
+  const double wc_ = div(pos ? -bm : bp, rw);
+  const double wl_ = pos ? wa : 0.0;
+  const double wr_ = pos ? 0.0 : wa;
+  F.pf = wl_ * L.p + wr_ * R.p + wc_ * cp;
+  const double frho = wl_ * fld + wr_ * frd;
+  F.fd = frho;
+  F.fmx = wl_ * (fld * L.vx) + wr_ * (frd * R.vx);
+  F.fmy = wl_ * (fld * L.vy) + wr_ * (frd * R.vy);
+  F.fmz = wl_ * (fld * L.vz) + wr_ * (frd * R.vz);
+  F.fe = wl_ * fle + wr_ * fre + wc_ * cp * am;
+  const bool up = (frho >= 0.0);
+  F.feg = frho * (up ? L.e : R.e);
+  F.vf = div(frho, pick(up, rdl, rdr));
+}
+
+// hllc_gas_fast behind a wave-uniform guard (the Cartesian tile march): the shock corrections ql, qr of the wave-speed
+// estimates are 1 wherever the interface pressure does not exceed the state's own (rarefactions, contacts, gas at
+// rest).  Where that holds for both states on every active lane, neither quotient nor root is formed (two v_rcp_f64, two
+// v_rsq_f64 and about forty fp64 instructions per face); otherwise the expressions and the selects of hllc_gas_fast.
+// A NaN pressure fails both comparisons and takes the roots as before.
+ADEV void hllc_gas_fast_skip(const double gm1, const double igm1, const double gamma, const double alpha,
+                             const Prim6 &L, const Prim6 &R, FaceFlux &F) {
+  const Recip rdl = recip(L.d), rdr = recip(R.d);
+  const double cl = sqrt_pos(div(gamma * L.p, rdl));
+  const double cr = sqrt_pos(div(gamma * R.p, rdr));
+  const double el = L.p * igm1 + 0.5 * L.d * (sqr(L.vx) + sqr(L.vy) + sqr(L.vz));
+  const double er = R.p * igm1 + 0.5 * R.d * (sqr(R.vx) + sqr(R.vy) + sqr(R.vz));
+  const double rc_avg = 0.25 * (L.d + R.d) * (cl + cr);
+  const double pmid = 0.5 * (L.p + R.p + (L.vx - R.vx) * rc_avg);
+  const bool weakl = (pmid <= L.p), weakr = (pmid <= R.p);
+  double ql = 1.0, qr = 1.0;
+  if (!__all(weakl && weakr)) {
+    ql = weakl ? 1.0 : sqrt_pos(1.0 + alpha * (div(pmid, L.p) - 1.0));
+    qr = weakr ? 1.0 : sqrt_pos(1.0 + alpha * (div(pmid, R.p) - 1.0));
+  }
   const double sl = L.vx - cl * ql;
   const double sr = R.vx + cr * qr;
   const double bp = sr > 0.0 ? sr : 1.0e-20;

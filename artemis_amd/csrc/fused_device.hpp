@@ -98,9 +98,12 @@ ADEV double slope(double qm, double q, double qp) {
 }
 // uniform-mesh slope with the division the caller may take (wave-uniform `fast`: no tiny velocity in reach, so the
 // hand-scheduled division gives the bits of `/`)
-template <int RECON>
+// SKIP (the Cartesian tile march): the hand-scheduled slope behind its wave-uniform guard (device_math.hpp
+// plm_dqm_fast_skip: no division in a wave whose slopes the limiter zeroes; same bits)
+template <int RECON, bool SKIP = false>
 ADEV double slope_sel(double qm, double q, double qp, bool fast) {
   if constexpr (RECON == 0) return 0.0;
+  else if constexpr (SKIP) return fast ? plm_dqm_fast_skip(qm, q, qp) : plm_dqm(qm, q, qp);
   else return fast ? plm_dqm_fast(qm, q, qp) : plm_dqm(qm, q, qp);
 }
 // a velocity the hand-scheduled divisions cannot take: non-zero and below 2^-200 (differences of admitted values are
@@ -144,7 +147,8 @@ ADEV GasK gas_constants(double gm1) {
   g.alpha = (g.gamma + 1.0) / (2.0 * g.gamma);
   return g;
 }
-template <int RIEMANN, int DIR>
+// SKIP (the Cartesian tile march): HLLC's shock corrections behind their wave-uniform guard (hllc_gas_fast_skip)
+template <int RIEMANN, int DIR, bool SKIP = false>
 ADEV Flux8 solve_face(const GasK &gk, const Cell6 &L, const Cell6 &R, const bool fast = true) {
   Prim6 l, r;
   l.d = L.d, l.p = L.p, l.e = L.e, r.d = R.d, r.p = R.p, r.e = R.e;
@@ -159,8 +163,10 @@ ADEV Flux8 solve_face(const GasK &gk, const Cell6 &L, const Cell6 &R, const bool
   if constexpr (RIEMANN == 0) {
     // wave-uniform: hllc_gas_fast's hand-scheduled divisions are the bits of hllc_gas's only while no numerator is
     // tiny (callers without that knowledge pass true and live with DESIGN.md section 4's limit)
-    if (fast) hllc_gas_fast(gk.gm1, gk.igm1, gk.gamma, gk.alpha, l, r, F);
-    else hllc_gas(gk.gm1, l, r, F);
+    if (fast) {
+      if constexpr (SKIP) hllc_gas_fast_skip(gk.gm1, gk.igm1, gk.gamma, gk.alpha, l, r, F);
+      else hllc_gas_fast(gk.gm1, gk.igm1, gk.gamma, gk.alpha, l, r, F);
+    } else hllc_gas(gk.gm1, l, r, F);
   } else if constexpr (RIEMANN == 1) { // (the same wave-uniform choice for HLLE and LLF)
     if (fast) hlle_gas_fast(gk.gm1, gk.igm1, gk.gamma, l, r, F);
     else hlle_gas(gk.gm1, l, r, F);

@@ -68,6 +68,12 @@ namespace {
 #ifndef ARTEMIS_PERI_PRIO
 #define ARTEMIS_PERI_PRIO 1
 #endif
+// Flat-wave skip of the Cartesian march: work whose result a whole wave discards is not done.
+// 0 = off; 1 = one wave-uniform guard per slope and one per HLLC face; 2 = one guard per direction (the six slopes of
+// a sweep together) and one per HLLC face.  Same bits in every setting.
+#ifndef ARTEMIS_FLAT_SKIP
+#define ARTEMIS_FLAT_SKIP 1
+#endif
 #ifndef ARTEMIS_FTY
 #define ARTEMIS_FTY 8
 #endif
@@ -253,6 +259,8 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
                        Flux8 &fx_lo, Flux8 &fy_lo, bool &flagged, const bool det FPROF_ARGS) {
   FPROF(0);
   constexpr bool PG = CURV && RECON == 1; // PLM_G instead of the uniform-mesh slope
+  constexpr int SKIP = CURV ? 0 : ARTEMIS_FLAT_SKIP; // flat-wave guards: the Cartesian march only
+  constexpr bool SK1 = (SKIP == 1), SK6 = (SKIP == 2 && RECON == 1), SKF = (SKIP != 0);
   bool fastp = true; // every division hand-scheduled (no tiny velocity in this plane's tile)
   // LDS ordering rule of this function (pattern 5): a store to S orders every later load of S
   // behind it -- the compiler cannot tell the members apart through run-time indices -- and a load that is used at
@@ -286,25 +294,39 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   }
   if constexpr (GUARD) flagged = (flag_ != 0), fastp = !flagged;
   double ux_[6], uy_[6]; // upper face values: stored after the last slope
-#define SLOPE(m, n, lm, rm, lov, upv, geo)                                                 \
+  // (FLAT: the direction's guard of ARTEMIS_FLAT_SKIP = 2 found the six slopes zero on every lane)
+#define SLOPE(m, n, lm, rm, lov, upv, geo, FLAT)                                           \
   {                                                                                        \
     double up_, lo_;                                                                       \
     if constexpr (PG) {                                                                    \
       if (fastp) plm_g_shared<2>(lm[n], qc.m, rm[n], up_, lo_, geo);                       \
       else plm_g_shared<0>(lm[n], qc.m, rm[n], up_, lo_, geo);                             \
     } else {                                                                               \
-      const double s_ = slope_sel<RECON>(lm[n], qc.m, rm[n], fastp);                       \
+      const double s_ = FLAT ? 0.0 : slope_sel<RECON, SK1>(lm[n], qc.m, rm[n], fastp);     \
       lo_ = lo_val<RECON>(qc.m, s_), up_ = up_val<RECON>(qc.m, s_);                        \
     }                                                                                      \
     lov.m = lo_;                                                                           \
     upv[n] = up_;                                                                          \
   }
-#define SLX(m, n) SLOPE(m, n, xm_, xp_, lox, ux_, gx.g1)
-#define SLY(m, n) SLOPE(m, n, ym_, yp_, loy, uy_, gx.g2)
-  SLX(d, 0) SLX(v1, 1) SLX(v2, 2) SLX(v3, 3) SLX(p, 4) SLX(e, 5)
-  if (multi_d) { SLY(d, 0) SLY(v1, 1) SLY(v2, 2) SLY(v3, 3) SLY(p, 4) SLY(e, 5) }
+#define FLAT6(lm, rm)                                                                      \
+  (fastp && __all(plm_flat(lm[0], qc.d, rm[0]) && plm_flat(lm[1], qc.v1, rm[1]) && plm_flat(lm[2], qc.v2, rm[2]) && \
+                  plm_flat(lm[3], qc.v3, rm[3]) && plm_flat(lm[4], qc.p, rm[4]) && plm_flat(lm[5], qc.e, rm[5])))
+#define SLX(m, n, F) SLOPE(m, n, xm_, xp_, lox, ux_, gx.g1, F)
+#define SLY(m, n, F) SLOPE(m, n, ym_, yp_, loy, uy_, gx.g2, F)
+#define SL6(S, F) S(d, 0, F) S(v1, 1, F) S(v2, 2, F) S(v3, 3, F) S(p, 4, F) S(e, 5, F)
+  if constexpr (SK6) {
+    if (FLAT6(xm_, xp_)) { SL6(SLX, true) } else { SL6(SLX, false) }
+    if (multi_d) {
+      if (FLAT6(ym_, yp_)) { SL6(SLY, true) } else { SL6(SLY, false) }
+    }
+  } else {
+    SL6(SLX, false)
+    if (multi_d) { SL6(SLY, false) }
+  }
+#undef SL6
 #undef SLX
 #undef SLY
+#undef FLAT6
 #undef SLOPE
 #pragma unroll
   for (int n = 0; n < 6; ++n) S.UPX[n][ty][tx + 1] = ux_[n];
@@ -317,14 +339,21 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   }
   // A perimeter duty: the six slopes of one cell outside the tile.  Its 18 values are requested before the first slope and
   // its six face values stored after the last (`geo`: the cell's PLM_G record, read only by the curvilinear kernel).
+  // (partial waves: the guards' __all looks at the duty lanes only)
 #define DUTY_SLOPES(geo)                                                                   \
+  bool flat_ = false;                                                                      \
+  if constexpr (SK6) {                                                                     \
+    bool f_ = true;                                                                        \
+    _Pragma("unroll") for (int n = 0; n < 6; ++n) f_ = f_ && plm_flat(pm_[n], pc_[n], pp_[n]); \
+    flat_ = fastp && __all(f_);                                                            \
+  }                                                                                        \
   _Pragma("unroll") for (int n = 0; n < 6; ++n) {                                          \
     double up_, lo_;                                                                       \
     if constexpr (PG) {                                                                    \
       if (fastp) plm_g_shared<2>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                   \
       else plm_g_shared<0>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                         \
     } else {                                                                               \
-      const double s_ = slope_sel<RECON>(pm_[n], pc_[n], pp_[n], fastp);                   \
+      const double s_ = flat_ ? 0.0 : slope_sel<RECON, SK1>(pm_[n], pc_[n], pp_[n], fastp); \
       lo_ = lo_val<RECON>(pc_[n], s_), up_ = up_val<RECON>(pc_[n], s_);                    \
     }                                                                                      \
     po_[n] = side ? lo_ : up_;                                                             \
@@ -370,12 +399,12 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   GET6(L, S.UPX, [ty][tx]);
   L2 = L;
   if (multi_d) { GET6(L2, S.UPY, [ty][tx]); }
-  fx_lo = solve_face<RIEMANN, 1>(x.gk, L, lox, fastp);
+  fx_lo = solve_face<RIEMANN, 1, SKF>(x.gk, L, lox, fastp);
   if constexpr (CURV) fx_lo.m2 *= gx.h1[1], fx_lo.m3 *= gx.h1[2]; // ScaleMomentumFlux (h1 == 1)
   if (tx > 0) { PUT8(S.FX, fx_lo, [ty][tx - 1]); }
   fy_lo = fx_lo;
   if (multi_d) {
-    fy_lo = solve_face<RIEMANN, 2>(x.gk, L2, loy, fastp);
+    fy_lo = solve_face<RIEMANN, 2, SKF>(x.gk, L2, loy, fastp);
     if constexpr (CURV) fy_lo.m2 *= gx.h2[1], fy_lo.m3 *= gx.h2[2];
     if (ty > 0) { PUT8(S.FY, fy_lo, [ty - 1][tx]); }
   }
@@ -399,7 +428,7 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
         a_ = r.v1;
         r.v1 = r.v2, r.v2 = r.v3, r.v3 = a_;
       }
-      Flux8 fe_ = solve_face<RIEMANN, 1>(x.gk, l, r, fastp);
+      Flux8 fe_ = solve_face<RIEMANN, 1, SKF>(x.gk, l, r, fastp);
       if (isx) {
         if constexpr (CURV) fe_.m2 *= S.HF1[u][0], fe_.m3 *= S.HF1[u][1]; // the face below cell (j0+u, i0+32)
         PUT8(S.FX, fe_, [u][FTX - 1]);
@@ -887,6 +916,8 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
   // the plane flags: PLM_G's cubic numerators need them in the curvilinear kernel; the flux TASK keeps every output
   // bit exact with them (the fused Cartesian stage does without: DESIGN.md section 4)
   constexpr bool GUARD = (CURV && RECON == 1) || FLUXES;
+  constexpr int SKIP = CURV ? 0 : ARTEMIS_FLAT_SKIP; // flat-wave guards of the x3 sweep (plane_sweeps: x1, x2)
+  [[maybe_unused]] constexpr bool SK1 = (SKIP == 1), SK6 = (SKIP == 2 && RECON == 1), SKF = (SKIP != 0);
   // the Cartesian stage: detect-and-redo instead of a second code path (which costs registers it does not have)
 #ifndef ARTEMIS_DETECT
 #define ARTEMIS_DETECT 1
@@ -963,7 +994,13 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
 #undef ZL0
       } else {
         const bool f0 = !(FLUXES && __any(tiny_v(qmm) || tiny_v(qc) || tiny_v(qn)));
-#define ZL0(m) zl.m = up_val<RECON>(qc.m, slope_sel<RECON>(qmm.m, qc.m, qn.m, f0));
+        bool flat_ = false;
+        if constexpr (SK6) {
+#define ZF0(m) &&plm_flat(qmm.m, qc.m, qn.m)
+          flat_ = f0 && __all(true FOR6(ZF0));
+#undef ZF0
+        }
+#define ZL0(m) zl.m = up_val<RECON>(qc.m, flat_ ? 0.0 : slope_sel<RECON, SK1>(qmm.m, qc.m, qn.m, f0));
         FOR6(ZL0)
 #undef ZL0
       }
@@ -1034,16 +1071,24 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
 #undef ZSL
         }
       } else {
-#define ZSL(m)                                                                             \
+#define ZSL(m, FLAT)                                                                       \
   {                                                                                        \
-    const double s_ = slope_sel<RECON>(qc.m, qn.m, qnn.m, fast_col);                       \
+    const double s_ = FLAT ? 0.0 : slope_sel<RECON, SK1>(qc.m, qn.m, qnn.m, fast_col);     \
     zr.m = lo_val<RECON>(qn.m, s_);                                                        \
     zl_next.m = up_val<RECON>(qn.m, s_);                                                   \
   }
-        FOR6(ZSL)
+#define ZSL6(F) ZSL(d, F) ZSL(v1, F) ZSL(v2, F) ZSL(v3, F) ZSL(p, F) ZSL(e, F)
+        if constexpr (SK6) {
+#define ZF(m) &&plm_flat(qc.m, qn.m, qnn.m)
+          if (fast_col && __all(true FOR6(ZF))) { ZSL6(true) } else { ZSL6(false) }
+#undef ZF
+        } else {
+          ZSL6(false)
+        }
+#undef ZSL6
 #undef ZSL
       }
-      Flux8 fz_hi = solve_face<RIEMANN, 3>(x.gk, zl, zr, fast_col);
+      Flux8 fz_hi = solve_face<RIEMANN, 3, SKF>(x.gk, zl, zr, fast_col);
       if constexpr (CURV) fz_hi.m2 *= gx.h3[1], fz_hi.m3 *= gx.h3[2]; // ScaleMomentumFlux at the x3 face
       FPROF(6);
       if (k >= k0) {
