@@ -960,6 +960,14 @@ int artemis_hip_stage_general_variant(const artemis_pack_t *p, const artemis_sta
                                         p->dust.riemann);
 }
 
+int artemis_hip_stage_general_dust_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a) {
+  if (!p || !a) return 0;
+  if (p->dust.nspecies == 0) return -1;
+  if (a->defer_finish < 0 || a->defer_finish > 2) return 0;
+  return artemis::stage_general_dust_variant(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon,
+                                             p->dust.riemann);
+}
+
 static int stage_epilogue_common(const artemis_pack_t *p, const artemis_stage_general_args_t *a, void *stream, bool to_cons) {
   if (int rc = validate(p)) return rc;
   if (!a) return fail(ARTEMIS_HIP_EINVAL, "null stage args");

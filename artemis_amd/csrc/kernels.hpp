@@ -109,6 +109,8 @@ void launch_ml_stage_fixup(const PackView &P, const artemis_stage_general_args_t
                            int recon_dust, int riemann_dust, const artemis_ml_fix_cell_t *cells, int ncells, hipStream_t s);
 int stage_general_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
                           int recon_dust, int riemann_dust);
+int stage_general_dust_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
+                          int recon_dust, int riemann_dust);
 bool stage2d_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas, int recon_dust,
                     int riemann_dust);
 void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas, int riemann_dust,

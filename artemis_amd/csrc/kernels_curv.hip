@@ -72,7 +72,7 @@ struct CurvK {
   int has_u1;
   int nti, ntj, nchunk, kchunk;
   int grav_on, rfc_on, diff_on;
-  double rf_omega;
+  double rf_omega, rf_qshear;           // (Cartesian instantiations: the shearing box's Omega0 and q)
   artemis_gravity_t grav;
   double *const *dsum;
   int to_cons;                          // 1: stop after the sources, conserved state to P.gas.cons0 (drag follows)
@@ -93,7 +93,7 @@ enum { PW_CR = 0, PW_CL, PW_UP, PW_LO, PW_RAB, PW_RAY, PW_RBB, PW_RBY, PW_NF, //
 // so the compiler parks them in VGPR lanes (v_writelane / v_readlane around every use) and, at 256 VGPRs, in scratch.
 // One thread copies them to LDS once; a use is a broadcast ds_read next to the instruction that consumes it.
 struct CurvConst {
-  double gam0, gam1, beta_dt, bdt, cfl, rf_omega, omf, nb_omf;
+  double gam0, gam1, beta_dt, bdt, cfl, rf_omega, rf_qshear, omf, nb_omf;
   double dfloor, siefloor, de_switch;
   artemis_gravity_t grav;
   // the block's output / viscous-sum / conserved arrays.  Read from the pointer tables inside the march they would be
@@ -135,6 +135,7 @@ struct CurvTile {
   double C3[CKMAX], S3[CKMAX];  // cos / sin of the x3 centres of the chunk's planes (spherical3D, axisymmetric; else 1 / 0)
   int tiny[2];                  // plane (k & 1) holds a tiny-but-nonzero velocity: its slopes take IEEE division
   double wmin[4];
+  double geom[6];               // the block's x1 / x2 / x3 origin and spacing (shear_terms of the Cartesian instantiations)
   CurvConst C;
 };
 static_assert(sizeof(CurvTile<32>) <= 80 * 1024 && sizeof(CurvTile<16>) <= 80 * 1024, "two workgroups per CU");
@@ -198,7 +199,8 @@ template <int SYS, int RIEMANN, int RECON, bool D3, int FTX, bool EXT = false, b
 __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, const CurvK a) {
   using T = CurvTile<FTX>;
   constexpr int FTY = T::FTY, QX = T::QX, QY = T::QY, FH = 2;
-  constexpr int NV = DUST ? 4 : 6; // staged variables; also the stride of the fluid's pointer tables (one species)
+  constexpr int NV = DUST ? 4 : 6; // staged variables (the gas tables' stride; the dust tables hold 4 ns pointers a block)
+  constexpr bool CART = (SYS == ARTEMIS_CARTESIAN); // no metric, no coordinate sources; rf_omega is the shearing box
   constexpr bool PG = (RECON == 1);                       // a limited slope (PLM): the tiny-velocity guard applies
   constexpr bool PGG = PG && SYS != ARTEMIS_CARTESIAN;    // PLM_G: the slope takes geometric weights (plm.hpp:54-73)
   __shared__ T S;
@@ -212,7 +214,14 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
   id /= a.nti;
   const int tj = id % a.ntj;
   id /= a.ntj;
-  const int chunk = id % a.nchunk, b = id / a.nchunk;
+  const int chunk = id % a.nchunk;
+  id /= a.nchunk;
+  // DUST: the species is the launch's slowest index (species are independent until drag: one march each, one launch)
+  const int nsd = DUST ? P.dust.ns : 1;
+  const int b = DUST ? id % P.nb : id, sp = DUST ? id / P.nb : 0;
+  // entry q (rho, v1, v2, v3[, P, sie]) of this block's -- and, dust, this species' -- part of a pointer table: a dust
+  // block holds the ns densities, then three velocity components per species
+  auto tix = [&](int q) { return DUST ? b * 4 * nsd + (q == 0 ? sp : nsd + 3 * sp + (q - 1)) : b * NV + q; };
   const bool multi_d = D3 || P.ndim > 1;
   const int i0 = P.is + ti * FTX, j0 = P.js + tj * FTY;
   const int i = i0 + tx, j = j0 + ty;
@@ -223,17 +232,19 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
   const double gm1 = P.gm1;
   const GasK gk = gas_constants(gm1);
   const FluidView &f = DUST ? P.dust : P.gas;
+  const double *g = P.geom + 6 * b;
   if (t == 0) { // (read back after the barrier that follows the geometry tables)
     CurvConst c;
     c.gam0 = a.gam0, c.gam1 = a.gam1, c.beta_dt = a.beta_dt, c.bdt = a.bdt, c.cfl = a.cfl, c.rf_omega = a.rf_omega;
+    c.rf_qshear = a.rf_qshear;
     if (a.bdt_ptr) c.beta_dt = c.bdt = *a.bdt_ptr;
     c.omf = P.omf, c.nb_omf = a.nb_omf;
     c.dfloor = f.dfloor, c.siefloor = f.siefloor, c.de_switch = f.de_switch;
     c.grav = a.grav;
-    for (int q = 0; q < NV; ++q) c.out[q] = a.prim_out[b * NV + q], c.cons0[q] = a.to_cons ? f.cons0[b * NV + q] : nullptr;
+    for (int q = 0; q < NV; ++q) c.out[q] = a.prim_out[tix(q)], c.cons0[q] = a.to_cons ? f.cons0[tix(q)] : nullptr;
     for (int q = 0; q < 5; ++q) c.dsum[q] = (!DUST && a.diff_on) ? a.dsum[b * 5 + q] : nullptr;
-    for (int q = 0; q < 4; ++q) c.u1[q] = a.prim_u1[b * NV + q];
-    c.u1[4] = a.prim_u1[b * NV + (DUST ? 0 : NV - 1)]; // (dust: never loaded)
+    for (int q = 0; q < 4; ++q) c.u1[q] = a.prim_u1[tix(q)];
+    c.u1[4] = a.prim_u1[tix(DUST ? 0 : NV - 1)]; // (dust: never loaded)
     S.C = c;
     if constexpr (DUST) {
       if (a.finish) { // (field by field, straight to LDS: an aggregate copy under this condition would live in scratch)
@@ -248,9 +259,8 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
       }
     }
   }
-  const double *g = P.geom + 6 * b;
-  const double *in_r = a.prim_in[b * NV + 0], *in_1 = a.prim_in[b * NV + 1], *in_2 = a.prim_in[b * NV + 2];
-  const double *in_3 = a.prim_in[b * NV + 3], *in_e = DUST ? in_r : a.prim_in[b * NV + (NV - 1)]; // (dust: never loaded)
+  const double *in_r = a.prim_in[tix(0)], *in_1 = a.prim_in[tix(1)], *in_2 = a.prim_in[tix(2)];
+  const double *in_3 = a.prim_in[tix(3)], *in_e = DUST ? in_r : a.prim_in[tix(NV - 1)]; // (dust: never loaded)
   const unsigned sj = static_cast<unsigned>(P.sj), sk = static_cast<unsigned>(P.sk);
   const unsigned col = static_cast<unsigned>(jl) * sj + static_cast<unsigned>(il);
   auto ldraw = [&](const double *r_, const double *v1_, const double *v2_, const double *v3_, const double *e_, unsigned c_) {
@@ -320,6 +330,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     }
   }
   if (t == 0) S.tiny[0] = S.tiny[1] = 0;
+  if (CART && t >= 32 && t < 38) S.geom[t - 32] = g[t - 32]; // (one lane each: nothing of it passes through scalar registers)
   if (t >= 64 && t < 64 + (k1 - k0 + 1)) { // (a second wave: the first fills the x3 weights)
     const int kk = k0 + (t - 64);
     S.C3[t - 64] = m3 ? m3[MT3_COS * (P.nk + 1) + kk] : 1.0, S.S3[t - 64] = m3 ? m3[MT3_SIN * (P.nk + 1) + kk] : 0.0;
@@ -415,11 +426,14 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
       s.tm[D - 1] = dtdx * (lo.pf - hi.pf);
       s.te[D - 1] = dt_vol * 0.5 * (lo.pf + hi.pf) * (A1 * hi.vf - A0 * lo.vf);
     }
-    // sources_device.hpp rotating_frame_divf / rotating_frame_gas (inactive directions enter as 0 * (0 + 0))
-    const double flo = on ? lo.d : 0.0, fup = on ? hi.d : 0.0, a0 = on ? A0 : 0.0, a1 = on ? A1 : 0.0;
-    const double term = (flo * a0 * W0 + fup * a1 * W1);
-    if constexpr (D == 1) s.rfd = term, s.rfx[0] = 0.5 * (flo + fup);
-    else s.rfd = s.rfd + (on ? 1 : 0) * term, s.rfx[D - 1] = (on ? 1 : 0) * 0.5 * (flo + fup);
+    // sources_device.hpp rotating_frame_divf / rotating_frame_gas (inactive directions enter as 0 * (0 + 0)); a Cartesian
+    // pack's rotating frame is the shearing box, which reads no flux: the sums are not formed
+    if constexpr (!CART) {
+      const double flo = on ? lo.d : 0.0, fup = on ? hi.d : 0.0, a0 = on ? A0 : 0.0, a1 = on ? A1 : 0.0;
+      const double term = (flo * a0 * W0 + fup * a1 * W1);
+      if constexpr (D == 1) s.rfd = term, s.rfx[0] = 0.5 * (flo + fup);
+      else s.rfd = s.rfd + (on ? 1 : 0) * term, s.rfx[D - 1] = (on ? 1 : 0) * 0.5 * (flo + fup);
+    }
   };
 
   auto update = [&](const int k, const DCoordsT<true> &co, const CellMetric &cm, const double hx[3], const Cell6 &qc, Sums &s,
@@ -446,7 +460,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
       u0.m2 = KC.gam0 * u0.m2 + KC.gam1 * u1.m2 + q2m;
       u0.m3 = KC.gam0 * u0.m3 + KC.gam1 * u1.m3 + q3m;
       const double dt = KC.bdt;
-      { // Dust::FluxSource (dust.cpp:303-326): the coordinate source only
+      if constexpr (!CART) { // Dust::FluxSource (dust.cpp:303-326): the coordinate source only
         const double rdt = w.rho * dt;
         double vf[3];
         rotation_velocity(co, KC.omf, vf);
@@ -465,7 +479,9 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
         nb_apply<false>(a.nb_pl, a.nb_n, co, KC.nb_omf, dt, wv, u);
         u0.d = u[0], u0.m1 = u[1], u0.m2 = u[2], u0.m3 = u[3];
       }
-      if (a.rfc_on) { // sources_device.hpp rotating_frame_dust on the folded sums
+      if constexpr (CART) { // RotatingFrame::ShearingBoxImpl: the terms of this column and plane, formed where they are used
+        if (a.rfc_on) shear_dust(shear_terms(S.geom, P.ndim, k, i, KC.rf_omega, KC.rf_qshear), dt, w, u0);
+      } else if (a.rfc_on) { // sources_device.hpp rotating_frame_dust on the folded sums
         const RotFrame rfc = rotating_frame_terms(co, KC.rf_omega, dt);
         const double qv = s.rfd / cm.vol;
         u0.m1 -= rfc.omdt * qv * rfc.ep[0];
@@ -558,7 +574,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
       u0.m3 += s.tm[2];
       u0.eg -= s.te[2];
     }
-    {
+    if constexpr (!CART) {
       const double rdt = w.rho * dt;
       double vf[3];
       rotation_velocity(co, KC.omf, vf);
@@ -587,7 +603,9 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
       nb_apply<true>(a.nb_pl, a.nb_n, co, KC.nb_omf, dt, wv, u);
       u0.d = u[0], u0.m1 = u[1], u0.m2 = u[2], u0.m3 = u[3], u0.e = u[4], u0.eg = u[5];
     }
-    if (a.rfc_on) { // sources_device.hpp rotating_frame_gas on the folded sums
+    if constexpr (CART) { // RotatingFrame::ShearingBoxImpl (the per-task shearing_box_kernel's device functions)
+      if (a.rfc_on) shear_gas(shear_terms(S.geom, P.ndim, k, i, KC.rf_omega, KC.rf_qshear), dt, w, u0);
+    } else if (a.rfc_on) { // sources_device.hpp rotating_frame_gas on the folded sums
       const RotFrame rfc = rotating_frame_terms(co, KC.rf_omega, dt);
       const double qv = __any(tiny_nonzero(s.rfd)) ? s.rfd / cm.vol : div(s.rfd, rvol); // (divf / vol)
       u0.m1 -= rfc.omdt * qv * rfc.ep[0];
@@ -829,8 +847,8 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
          dt_vol, multi_d);
     double hx[3];
     scale_factors_of(co, hx);
-    s.tm[2] = s.te[2] = 0.0, s.rfx[2] = 0 * 0.5 * (0.0 + 0.0);
-    s.rfd = s.rfd + 0 * (0.0 * 0.0 * 0.0 + 0.0 * 0.0 * 0.0);
+    s.tm[2] = s.te[2] = 0.0;
+    if constexpr (!CART) s.rfx[2] = 0 * 0.5 * (0.0 + 0.0), s.rfd = s.rfd + 0 * (0.0 * 0.0 * 0.0 + 0.0 * 0.0 * 0.0);
     update(k0, co, cm, hx, qc, s, u1raw, ds, gcz);
   } else {
     Cell6 qc = ldcell(in_r, in_1, in_2, in_3, in_e, col + static_cast<unsigned>(k0 - 1) * sk);
@@ -1010,19 +1028,24 @@ void launch_sys(const PackView &P, const CurvK &k, int riemann, int recon, bool 
 }
 } // namespace
 
-// Gas (one species) on a non-Cartesian system, PCM / PLM, with the pointwise tasks the kernel folds in; diffusion only
-// as artemis_hip_viscous_source's sums (the flux-array form stays on kernels_fused.hip's instantiation).  A dust
-// species beside it, drag and N-body gravity are fine: the dust runs on its cell-centred kernel and the drag finish
-// couples the two (launch_stage_cell).
+// Gas (one species), PCM / PLM, with the pointwise tasks the kernel folds in; diffusion only as
+// artemis_hip_viscous_source's sums (the flux-array form stays on kernels_fused.hip's instantiation).  Dust species
+// beside it, drag and N-body gravity are fine: the dust runs on its own march (curv_march_covers_dust) or on its
+// cell-centred kernel, and the drag finish couples the fluids (launch_stage_cell).
 bool curv_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas) {
   if (opt(OPT_NO_CURV_MARCH)) return false;
   if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false;
-  if (P.gas.ns != 1 || P.dust.ns > 1 || P.ng < 2) return false;
+  if (P.gas.ns != 1 || P.dust.ns > ARTEMIS_MAX_DUST_SPECIES || P.ng < 2) return false;
   // Cartesian packs with the pointwise sources the tuned kernel (kernels_fused.hip) and the 2-D row march do not carry --
-  // gravity, viscosity as sums -- on the same march: plain PLM, every metric factor 1 (SYS = cartesian instantiations);
-  // the rotating frame of a Cartesian pack is the shearing box, which this march does not have
-  if (P.coords == ARTEMIS_CARTESIAN && (P.dust.ns != 0 || g.rf_omega != 0.0 || g.nbody_n || P.ndim < 2 || opt(OPT_NO_CART_MARCH)))
+  // gravity, viscosity as sums, the shearing box (a Cartesian pack's rotating frame), dust species beside the gas -- on
+  // the same march: plain PLM, every metric factor 1 (SYS = cartesian instantiations)
+  if (P.coords == ARTEMIS_CARTESIAN && (g.nbody_n || P.ndim < 2 || opt(OPT_NO_CART_MARCH))) return false;
+  // NO_CART_DUST_MARCH: Cartesian packs with dust or the shearing box, and packs with several dust species on any
+  // system, keep the kernels they had before the march took them
+  if (opt(OPT_NO_CART_DUST_MARCH) &&
+      (P.dust.ns > 1 || (P.coords == ARTEMIS_CARTESIAN && (P.dust.ns != 0 || g.rf_omega != 0.0))))
     return false;
+  if (g.strat_faces) return false; // (conditions inside the kernel: the row march only)
   if (!g.pcm && recon_gas == ARTEMIS_PPM) return false;
   if (g.cooling) return false;
   if (g.diffusion && !g.diffusion_sums) return false;
@@ -1043,9 +1066,9 @@ bool curv_march_covers(const PackView &P, const artemis_stage_general_args_t &g,
   }
 }
 
-// The dust species beside it on the same march (DUST instantiations): PCM / PLM, HLLE / LLF
+// The dust species beside it on the same march (DUST instantiations, one launch for all species): PCM / PLM, HLLE / LLF
 bool curv_march_covers_dust(const PackView &P, const artemis_stage_general_args_t &g, int recon_dust, int riemann_dust) {
-  if (P.dust.ns != 1 || opt(OPT_NO_CURV_DUST_MARCH)) return false;
+  if (P.dust.ns < 1 || opt(OPT_NO_CURV_DUST_MARCH)) return false;
   if (!g.pcm && recon_dust == ARTEMIS_PPM) return false;
   return riemann_dust == ARTEMIS_HLLE || riemann_dust == ARTEMIS_LLF;
 }
@@ -1086,10 +1109,11 @@ void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g,
   k.nchunk = (P.ndim > 2) ? (nz + k.kchunk - 1) / k.kchunk : 1;
   k.grav_on = (g.gravity && (g.time >= g.gravity->tstart) && (g.time < g.gravity->tstop)) ? 1 : 0;
   if (k.grav_on) k.grav = *g.gravity;
-  k.rfc_on = (g.rf_omega != 0.0) ? 1 : 0, k.rf_omega = g.rf_omega;
+  k.rfc_on = (g.rf_omega != 0.0) ? 1 : 0, k.rf_omega = g.rf_omega, k.rf_qshear = g.rf_qshear;
   k.diff_on = (!dust && g.diffusion != nullptr) ? 1 : 0;
   k.dsum = dust ? nullptr : g.diffusion_sums;
-  const unsigned grid = static_cast<unsigned>(tiles * k.nchunk);
+  // (dust: every species marches the same tiles and chunks in the same launch, the species as the grid's slowest index)
+  const unsigned grid = static_cast<unsigned>(tiles * k.nchunk * (dust ? P.dust.ns : 1));
   const int recon = g.pcm ? ARTEMIS_PCM : recon_in;
   const bool d3 = P.ndim > 2;
 #define CURV_SYS(SYSV, D3V)                                                          \
@@ -1098,9 +1122,9 @@ void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g,
     else launch_sys<SYSV, D3V>(P, k, riemann, recon, narrow, grid, s);               \
   } while (0)
   switch (P.coords) {
-  case ARTEMIS_CARTESIAN: // (gas only: curv_march_covers)
-    if (d3) launch_sys<ARTEMIS_CARTESIAN, true>(P, k, riemann, recon, narrow, grid, s);
-    else launch_sys<ARTEMIS_CARTESIAN, false>(P, k, riemann, recon, narrow, grid, s);
+  case ARTEMIS_CARTESIAN: // (2-D and 3-D: curv_march_covers)
+    if (d3) CURV_SYS(ARTEMIS_CARTESIAN, true);
+    else CURV_SYS(ARTEMIS_CARTESIAN, false);
     break;
   case ARTEMIS_CYLINDRICAL:
     if (d3) CURV_SYS(ARTEMIS_CYLINDRICAL, true);

@@ -665,6 +665,23 @@ int stage_general_variant(const PackView &P, const artemis_stage_general_args_t 
   return 0;
 }
 
+// One dust species coupled by simple_dust drag: the dust march does the coupled update, SetAuxillaryFields and
+// ConsToPrim of both fluids on its registers (no conserved round trip of the dust, no finish launch)
+static bool dust_finish_in_march(const PackView &P, const artemis_stage_general_args_t &g) {
+  return g.drag && g.defer_finish != 1 && !opt(OPT_NO_DRAG_IN_MARCH) && drag_finish_in_march(P, *g.drag);
+}
+
+// Which kernel the DUST of this call runs on: -1 no dust; 0 cell-centred; 1 row march; 3 dust march; 5 dust march with
+// the drag finish inside it
+int stage_general_dust_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
+                               int recon_dust, int riemann_dust) {
+  if (P.dust.ns == 0) return -1;
+  const int variant = stage_general_variant(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust);
+  if (variant == 1) return 1;
+  if (variant != 3 || !curv_march_covers_dust(P, g, recon_dust, riemann_dust)) return 0;
+  return dust_finish_in_march(P, g) ? 5 : 3;
+}
+
 void launch_stage_cell(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas,
                        int riemann_gas, int recon_dust, int riemann_dust, hipStream_t s) {
   // 2-D Cartesian gas (+ <= 2 dust species) with the pointwise sources: the row-march kernel does the whole
@@ -688,7 +705,7 @@ void launch_stage_cell(const PackView &P, const artemis_stage_general_args_t &g,
   const bool to_cons = g.drag || defer;
   CellStageArgs a = cell_args(P, g);
   a.to_cons = to_cons ? 1 : 0;
-  if (variant == 3) { // curvilinear gas: the streaming tile march with its geometry in LDS tables (kernels_curv.hip)
+  if (variant == 3) { // the streaming tile march with its geometry in LDS tables (kernels_curv.hip)
     launch_stage_curv(P, g, 0, recon_gas, riemann_gas, s);
   } else if (P.gas.ns) {
     a.in = g.gas_in, a.u1 = g.gas_u1, a.out = g.gas_out;
@@ -698,10 +715,8 @@ void launch_stage_cell(const PackView &P, const artemis_stage_general_args_t &g,
     else launch_recon<0, 2>(P, recon, a, s);
   }
   const bool dust_march = variant == 3 && curv_march_covers_dust(P, g, recon_dust, riemann_dust);
-  // one dust species coupled by simple_dust drag: the dust march does the coupled update, SetAuxillaryFields and
-  // ConsToPrim of both fluids on its registers (no conserved round trip of the dust, no finish launch)
-  const bool finish_in_march = dust_march && g.drag && !defer && !opt(OPT_NO_DRAG_IN_MARCH) && drag_finish_in_march(P, *g.drag);
-  if (dust_march) { // the dust species on the same march (kernels_curv.hip, DUST instantiations)
+  const bool finish_in_march = dust_march && dust_finish_in_march(P, g);
+  if (dust_march) { // every dust species on the same march, one launch (kernels_curv.hip, DUST instantiations)
     launch_stage_curv(P, g, 1, recon_dust, riemann_dust, s, finish_in_march);
   } else if (P.dust.ns) {
     a.in = g.dust_in, a.u1 = g.dust_u1, a.out = g.dust_out;

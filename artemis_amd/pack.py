@@ -225,6 +225,8 @@ class MeshBlockPack:
         self._last_general_args = a
         # which kernel this call takes (0 cell-centred, 1 2-D row march, 2 / 3 curvilinear streaming tile, 4 PPM tile march)
         self.last_stage_variant = self.L.artemis_hip_stage_general_variant(C.byref(self.pack), C.byref(a))
+        # ... and the kernel its dust takes (-1 no dust, 0 cell-centred, 1 row march, 3 dust tile march, 5 with the drag finish)
+        self.last_dust_stage_variant = self.L.artemis_hip_stage_general_dust_variant(C.byref(self.pack), C.byref(a))
         self._call(self.L.artemis_hip_stage_general, C.byref(a))
 
     # ---- refined meshes on the one-kernel stages (include/artemis_hip.h "flux correction as a thin fix-up") ----

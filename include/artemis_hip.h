@@ -43,7 +43,9 @@
  *    NO_TUNED, TUNED_2D, NO_STAGE2D, NO_FUSED_CURV, NO_CURV_MARCH, NO_CURV_DUST, NO_CURV_DUST_MARCH, NO_DRAG_IN_MARCH
  *    (the drag finish as its own launch instead of inside the dust march), NO_STRAT_IN_KERNEL (the `strat` conditions as
  *    boundary-fill launches instead of inside the 2-D row march), NO_CART_MARCH (Cartesian packs with gravity / viscosity on
- *    the cell-centred stage instead of the tile march of kernels_curv.hip), NO_PPM_MARCH (one gas species with PPM on
+ *    the cell-centred stage instead of the tile march of kernels_curv.hip), NO_CART_DUST_MARCH (Cartesian packs with dust
+ *    species or the shearing box, and packs of any system with several dust species, on the kernels they ran before the
+ *    tile march took them: the cell-centred stage, or the older curvilinear march), NO_PPM_MARCH (one gas species with PPM on
  *    Cartesian 3-D blocks on the cell-centred stage instead of the PPM tile march of kernels_ppm.hip), NO_IC_IN_SHELL (`ic` faces as their own
  *    boundary-fill launches instead of inside the one-launch fill of the copy-type conditions), NO_IC_SKIP (host driver, refined
  *    meshes: `ic` faces refilled at every ghost fill although their zones never change), NO_ML_FUSED,
@@ -629,9 +631,13 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
                               void *stream);
 /* Which kernel artemis_hip_stage_general runs for this pack and these arguments (no launch, no device
  * access): 0 = the cell-centred kernels (one per fluid, + the drag finish), 1 = the 2-D row-march kernel
- * (kernels_stage2d.hip: both fluids, drag, aux, ConsToPrim and dt in one launch), 3 = the curvilinear tile march
- * (kernels_curv.hip: gas on any non-Cartesian system, geometry in LDS tables, two waves per SIMD; diffusion only as
- * diffusion_sums), 2 = its predecessor with the geometry in registers (kernels_fused.hip: taken when the diffusion
+ * (kernels_stage2d.hip: both fluids, drag, aux, ConsToPrim and dt in one launch), 3 = the tile march of kernels_curv.hip
+ * (one gas species, PCM / PLM, geometry in LDS tables, two waves per SIMD; diffusion only as diffusion_sums): gas on any
+ * non-Cartesian system, and on 2-D / 3-D Cartesian packs that carry what the tuned Cartesian kernels do not -- gravity,
+ * viscosity as sums, the shearing box (rf_omega != 0), up to ARTEMIS_MAX_DUST_SPECIES dust species beside the gas, drag,
+ * defer_finish -- unless the row march (1) takes the call first; Cartesian packs with N-body gravity, cooling or 1-D
+ * blocks stay on 0.  Where the dust of such a call runs is artemis_hip_stage_general_dust_variant's answer.
+ * 2 = its predecessor with the geometry in registers (kernels_fused.hip: taken when the diffusion
  * fluxes come from stored arrays), 4 = the PPM tile march (kernels_ppm.hip: one gas species alone on Cartesian 3-D
  * blocks, gas.recon = PPM and pcm = 0, nghost >= 3, none of the optional tasks -- gravity, rotating frame, drag,
  * diffusion, cooling, N-body, strat_faces -- and defer_finish = 0; any block extents, any number of blocks, gas_u1 equal
@@ -639,6 +645,15 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
  * blocks and curvilinear systems keep the variant they had).  Same results either way; benchmarks name the kernel they
  * timed with this.  A defer_finish outside 0 .. 2 gives 0 here and ARTEMIS_HIP_EINVAL from artemis_hip_stage_general. */
 int artemis_hip_stage_general_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a);
+/* Which kernel the DUST species of that call run on (no launch, no device access): -1 = the pack has no dust; 0 = the
+ * cell-centred dust kernels (dust with PPM or HLLC, NO_CURV_DUST_MARCH, or a gas variant of 0 / 2); 1 = the 2-D row
+ * march, together with the gas; 3 = the dust instantiations of the tile march (kernels_curv.hip: PCM / PLM, HLLE / LLF,
+ * every species in one launch, the species as the grid's slowest index), stopping at the new primitives or, with drag
+ * or defer_finish = 1, at the conserved state; 5 = the same march with the drag finish inside it (ONE dust species
+ * coupled by simple_dust drag without damping: DragSource, SetAuxillaryFields, ConsToPrim and both fluids' timestep
+ * limits on the march's registers; NO_DRAG_IN_MARCH gives 3).  3 and 5 occur only where
+ * artemis_hip_stage_general_variant is 3. */
+int artemis_hip_stage_general_dust_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a);
 /* The cell-local remainder of a stage in ONE pass over stored fluxes: after Gas/Dust::CalculateFluxes
  * (and the diffusion-flux tasks) have filled flux / pflux / vface (/ diff_flux) for p's primitives,
  * this does ApplyUpdate on cons0 / cons1, FluxSource, DiffusionUpdate, ExternalGravity,
