@@ -4,7 +4,8 @@
 //   frame velocity) -> DiffusionUpdate (from artemis_hip_viscous_source's sums) -> ExternalGravity -> RotatingFrameImpl
 //   -> SetAuxillaryFields -> ConsToPrim (-> EstimateTimestepMesh)
 // (artemis_driver.cpp:182-255; plm.hpp:54-73, fluid_fluxes.hpp:33-70, :323-417) in ONE pass: the 2.5-D tile march of
-// kernels_fused.hip -- a 256-thread workgroup owns an FTX x FTY column of zones and marches along x3, rolling window,
+// kernels_fused.hip (what the marches share: march_device.hpp) -- a 256-thread workgroup owns an FTX x FTY column of
+// zones and marches along x3, rolling window,
 // carried x3 face state and flux in registers, x2 exchange through LDS, two barriers per plane, perimeter duties
 // rotating over the waves -- rebuilt around the one thing that kept its curvilinear instantiation at one wave per SIMD:
 //
@@ -36,6 +37,7 @@
 #include "fused_device.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "march_device.hpp"
 #include "options.hpp"
 #include "pack_view.hpp"
 #include "sources_device.hpp"
@@ -169,25 +171,8 @@ ADEV Flux8 solve_fluid(const GasK &gk, const Cell6 &L, const Cell6 &R, const boo
   }
 }
 // The dust instantiation (DUST) carries rho, v1, v2, v3 only: the pressure / energy slots of the staged cell and the
-// energy / pressure-flux / face-velocity slots of a face flux are skipped (every X body below is guarded by its index).
-#define CFOR6(X) X(d, 0) X(v1, 1) X(v2, 2) X(v3, 3) X(p, 4) X(e, 5)
-// ... with a scheduling fence after the third variable: three slope chains interleave (six would need the registers of
-// twelve more doubles)
-#define CFOR6_33(X) X(d, 0) X(v1, 1) X(v2, 2) __builtin_amdgcn_sched_barrier(0); X(v3, 3) X(p, 4) X(e, 5)
-#define CGET6(dst, A, ...)                                                                 \
-  dst.d = A[0] __VA_ARGS__, dst.v1 = A[1] __VA_ARGS__, dst.v2 = A[2] __VA_ARGS__,          \
-  dst.v3 = A[3] __VA_ARGS__;                                                               \
-  if constexpr (!DUST) dst.p = A[4] __VA_ARGS__, dst.e = A[5] __VA_ARGS__
-#define CPUT8(A, fl, ...)                                                                  \
-  A[0] __VA_ARGS__ = fl.d, A[1] __VA_ARGS__ = fl.m1, A[2] __VA_ARGS__ = fl.m2,             \
-  A[3] __VA_ARGS__ = fl.m3;                                                                \
-  if constexpr (!DUST)                                                                     \
-  A[4] __VA_ARGS__ = fl.e, A[5] __VA_ARGS__ = fl.eg, A[6] __VA_ARGS__ = fl.pf, A[7] __VA_ARGS__ = fl.vf
-#define CGET8(fl, A, ...)                                                                  \
-  fl.d = A[0] __VA_ARGS__, fl.m1 = A[1] __VA_ARGS__, fl.m2 = A[2] __VA_ARGS__,             \
-  fl.m3 = A[3] __VA_ARGS__;                                                                \
-  if constexpr (!DUST)                                                                     \
-  fl.e = A[4] __VA_ARGS__, fl.eg = A[5] __VA_ARGS__, fl.pf = A[6] __VA_ARGS__, fl.vf = A[7] __VA_ARGS__
+// energy / pressure-flux / face-velocity slots of a face flux are skipped (march_device.hpp's field lists take NV; every
+// X body below is guarded by its index).
 
 // (x1 neighbours: lane_below / lane_above, fused_device.hpp)
 
@@ -205,11 +190,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
   constexpr bool PGG = PG && SYS != ARTEMIS_CARTESIAN;    // PLM_G: the slope takes geometric weights (plm.hpp:54-73)
   __shared__ T S;
   const int t = threadIdx.x, tx = t % FTX, ty = t / FTX;
-  int id = blockIdx.x;
-  {
-    const int n = static_cast<int>(gridDim.x), q = n >> 3, rem = n & 7, xcd = id & 7;
-    id = xcd * q + min(xcd, rem) + (id >> 3);
-  }
+  int id = xcd_dealt_id();
   const int ti = id % a.nti;
   id /= a.nti;
   const int tj = id % a.ntj;
@@ -288,11 +269,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     const int u = t - 4 * FTX, cc = u & 3;
     hr = (u >> 2) + FH, hc = (cc < 2) ? cc : FTX + cc;
   }
-  unsigned hcol = col; // (threads without a halo duty: their own column)
-  if (hr >= 0) {
-    const int gi = min(max(i0 - FH + hc, 0), P.ni - 1), gj = min(max(j0 - FH + hr, 0), P.nj - 1);
-    hcol = static_cast<unsigned>(gj) * sj + static_cast<unsigned>(gi);
-  }
+  const unsigned hcol = halo_column<FH>(hr, hc, i0, j0, P.ni, P.nj, sj, col);
   // ---- the workgroup's geometry tables -----------------------------------------------------------------------------
   geotabs_fill(S.G, P, b, i0 - FH, j0 - FH, t);
   if constexpr (PGG) {
@@ -380,13 +357,13 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
   };
   auto stage_plane = [&](const Cell6 &q, const Raw5 &hal, int par) {
 #define PUTQ(m, n) if constexpr (n < NV) S.Q[n][ty + FH][tx + FH] = q.m;
-    CFOR6(PUTQ)
+    FOR6(PUTQ)
 #undef PUTQ
     bool tny = tiny_vel3(q.v1, q.v2, q.v3);
     if (hr >= 0) {
       const Cell6 h = finish_cell(hal, gm1);
 #define PUTH(m, n) if constexpr (n < NV) S.Q[n][hr][hc] = h.m;
-      CFOR6(PUTH)
+      FOR6(PUTH)
 #undef PUTH
       tny = tny || tiny_vel3(hal.v1, hal.v2, hal.v3);
     }
@@ -646,14 +623,8 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     gst(KC.out[3], c, n3);
     gst(KC.out[4], c, amax(0.0, gm1 * w_d * w_s)); // fill_derived.cpp:247 (consumers recompute it anyway)
     gst(KC.out[5], c, w_s);
-    if (a.dt_bits) { // Gas::EstimateTimestepMesh on the new state (gas.cpp:411-433)
-      const double bulk = (gm1 + 1.0) * gm1 * w_d * w_s;
-      const double cs = sqrt_pos(div(bulk, rwd));
-      double denom = div(fabs(n1) + cs, co.width1());
-      if (multi_d) denom += div(fabs(n2) + cs, co.width2());
-      if (D3) denom += div(fabs(n3) + cs, co.width3());
-      ldt = amin(ldt, div(1.0, denom));
-    }
+    // Gas::EstimateTimestepMesh on the new state
+    if (a.dt_bits) ldt = amin(ldt, zone_dt_term(w_d, n1, n2, n3, w_s, rwd, gm1, co, multi_d, D3));
   };
 
   // ---- one plane, phases 1 and 2: the x1 / x2 sweeps (two barriers) ----------------------------------------------------
@@ -677,7 +648,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     L.m = lane_below(up_);                                                                        \
     if (tx == FTX - 1) S.UPXE[n][ty] = up_;                                                       \
   }
-      CFOR6_33(SLX)
+      FOR6_33(SLX)
 #undef SLX
     }
     __builtin_amdgcn_sched_barrier(0); // (one sweep's six chains interleave; two sweeps' would not fit the registers)
@@ -690,7 +661,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     faces_of(FT, S.Q[n][ty + FH - 1][tx + FH], qc.m, S.Q[n][ty + FH + 1][tx + FH], r, up_, loy.m); \
     S.UPY[n][ty + 1][tx] = up_;                                                                   \
   }
-      CFOR6_33(SLY)
+      FOR6_33(SLY)
 #undef SLY
     }
     if (duty >= 128 && duty < 128 + 2 * FTY) { // columns i0-1 (upper value) and i0+FTX (lower value)
@@ -723,7 +694,7 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     __syncthreads();
     PROF(2);
     // ---- P2: Riemann problems at the own lower faces; the tile's upper perimeter on one duty wave --------------------
-    if (tx == 0) { CGET6(L, S.UPX0, [ty]); }
+    if (tx == 0) { GET6(NV, L, S.UPX0, [ty]); }
     fx_lo = solve_fluid<DUST, RIEMANN, 1>(gk, L, lox, fastp);
     {
       double h[3];
@@ -732,12 +703,12 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     }
     fy_lo = fx_lo;
     if (multi_d) {
-      CGET6(L, S.UPY, [ty][tx]);
+      GET6(NV, L, S.UPY, [ty][tx]);
       fy_lo = solve_fluid<DUST, RIEMANN, 2>(gk, L, loy, fastp);
       double h[3];
       CO(tx + FH, ty + FH, k).face_scale(2, h);
       fy_lo.m2 *= h[1], fy_lo.m3 *= h[2];
-      if (ty > 0) { CPUT8(S.FY, fy_lo, [ty - 1][tx]); }
+      if (ty > 0) { PUT8(NV, S.FY, fy_lo, [ty - 1][tx]); }
     }
     if (duty >= 64 && duty < 128) { // lanes 0 .. FTY-1: x1 face i0+FTX per row; lanes 32 .. 32+FTX-1: x2 face j0+FTY
       // ONE Riemann pass for both kinds of face (kernels_fused.hip): the x2 lanes rotate their velocity components
@@ -747,28 +718,26 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
         const int cx = u - 32;
         Cell6 l, r;
         if (isx) {
-          CGET6(l, S.UPXE, [u]);
-          CGET6(r, S.LOXE, [u]);
+          GET6(NV, l, S.UPXE, [u]);
+          GET6(NV, r, S.LOXE, [u]);
         } else {
-          CGET6(l, S.UPY, [FTY][cx]);
-          CGET6(r, S.LOY, [cx]);
-          double a_ = l.v1;
-          l.v1 = l.v2, l.v2 = l.v3, l.v3 = a_;
-          a_ = r.v1;
-          r.v1 = r.v2, r.v2 = r.v3, r.v3 = a_;
+          GET6(NV, l, S.UPY, [FTY][cx]);
+          GET6(NV, r, S.LOY, [cx]);
+          rotate_x2_in(l), rotate_x2_in(r);
         }
         Flux8 fe_ = solve_fluid<DUST, RIEMANN, 1>(gk, l, r, fastp);
         double h[3];
         if (isx) {
           CO(FTX + FH, u + FH, k).face_scale(1, h); // the face below zone (j0+u, i0+FTX)
           fe_.m2 *= h[1], fe_.m3 *= h[2];
-          CPUT8(S.FXE, fe_, [u]);
+          PUT8(NV, S.FXE, fe_, [u]);
         } else {
+          // (march_device.hpp rotate_x2_out, its text in place: as a call it moves the assembly of this file's kernels)
           const double n_ = fe_.m1; // (normal, t1, t2) = (m2, m3, m1) of the block's frame
           fe_.m1 = fe_.m3, fe_.m3 = fe_.m2, fe_.m2 = n_;
           CO(cx + FH, FTY + FH, k).face_scale(2, h); // the face below zone (j0+FTY, i0+cx)
           fe_.m2 *= h[1], fe_.m3 *= h[2];
-          CPUT8(S.FY, fe_, [FTY - 1][cx]);
+          PUT8(NV, S.FY, fe_, [FTY - 1][cx]);
         }
       }
     }
@@ -792,15 +761,10 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
   // ---- after the second barrier: the upper x1 / x2 faces from the neighbours; everything folded with ONE rebuild of the
   // zone's Coords / CellMetric from the tables (nothing of them crosses a barrier) ----------------------------------
   auto upper12 = [&](const Flux8 &fx_lo, Flux8 &fx_hi, Flux8 &fy_hi) {
-    fx_hi.d = lane_above(fx_lo.d), fx_hi.m1 = lane_above(fx_lo.m1), fx_hi.m2 = lane_above(fx_lo.m2);
-    fx_hi.m3 = lane_above(fx_lo.m3);
-    if constexpr (!DUST) {
-      fx_hi.e = lane_above(fx_lo.e), fx_hi.eg = lane_above(fx_lo.eg);
-      fx_hi.pf = lane_above(fx_lo.pf), fx_hi.vf = lane_above(fx_lo.vf);
-    }
-    if (tx == FTX - 1) { CGET8(fx_hi, S.FXE, [ty]); }
+    flux_from_lane_above<NV>(fx_lo, fx_hi);
+    if (tx == FTX - 1) { GET8(NV, fx_hi, S.FXE, [ty]); }
     fy_hi = fx_hi;
-    if (multi_d) { CGET8(fy_hi, S.FY, [ty][tx]); }
+    if (multi_d) { GET8(NV, fy_hi, S.FY, [ty][tx]); }
   };
 
   // ---- the march ------------------------------------------------------------------------------------------------------
@@ -860,11 +824,11 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
       if constexpr (PGG) r = rec_x3(tx + FH, ty + FH, k0 - 1);
       double unused_;
 #define ZL0(m, n) if constexpr (n < NV) faces_of(std::false_type{}, qmm.m, qc.m, qn.m, r, zl.m, unused_);
-      CFOR6(ZL0)
+      FOR6(ZL0)
 #undef ZL0
     }
 #define ZPUT(m, n) if constexpr (n < NV) S.ZL[n][t] = zl.m;
-    CFOR6(ZPUT)
+    FOR6(ZPUT)
     Flux8 fz_lo;
     fz_lo.d = fz_lo.m1 = fz_lo.m2 = fz_lo.m3 = fz_lo.e = fz_lo.eg = fz_lo.pf = fz_lo.vf = 0.0;
     Raw5 hal = u1raw; // halo zone of plane k+1 (staged by trip k)
@@ -915,15 +879,15 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
         PlmG r{};
         if constexpr (PGG) r = rec_x3(tx + FH, ty + FH, k + 1);
 #define ZSL(m, n) if constexpr (n < NV) faces_of(FT, qc.m, qn.m, qnn.m, r, zl_next.m, zr.m);
-        CFOR6_33(ZSL)
+        FOR6_33(ZSL)
 #undef ZSL
         Cell6 zl; // (written by this thread in the previous trip: no barrier needed)
 #define ZGET(m, n) if constexpr (n < NV) zl.m = S.ZL[n][t];
-        CFOR6(ZGET)
+        FOR6(ZGET)
 #undef ZGET
         fz_hi = solve_fluid<DUST, RIEMANN, 3>(gk, zl, zr, true);
         zl = zl_next;
-        CFOR6(ZPUT)
+        FOR6(ZPUT)
       };
       bool fast3 = true;
       if constexpr (PG) {
@@ -964,26 +928,9 @@ __global__ __launch_bounds__(256, 2) void stage_curv_kernel(const PackView P, co
     for (int q = 0; q < 10; ++q) atomicAdd(&g_curv_prof[q], prof_acc[q]);
 #endif
   if (a.dt_bits) {
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) ldt = fmin(ldt, __shfl_down(ldt, off, 64));
-    if ((t & 63) == 0) S.wmin[t >> 6] = ldt;
-    __syncthreads();
-    if (t == 0) {
-      double m = S.wmin[0];
-      for (int w = 1; w < 4; ++w) m = fmin(m, S.wmin[w]);
-      if (m < DBL_MAX) atomicMin(a.dt_bits, static_cast<unsigned long long>(__double_as_longlong(S.C.cfl * m)));
-    }
-    if constexpr (DUST) if (a.finish) { // ... and the gas fluid's limit of the same zones
-      __syncthreads();
-      for (int off = 32; off > 0; off >>= 1) ldt_gas = fmin(ldt_gas, __shfl_down(ldt_gas, off, 64));
-      if ((t & 63) == 0) S.wmin[t >> 6] = ldt_gas;
-      __syncthreads();
-      if (t == 0) {
-        double m = S.wmin[0];
-        for (int w = 1; w < 4; ++w) m = fmin(m, S.wmin[w]);
-        if (m < DBL_MAX) atomicMin(a.dt_bits, static_cast<unsigned long long>(__double_as_longlong(S.C.cfl_gas * m)));
-      }
-    }
+    BLOCK_MIN_TO_DT(t, ldt, S.wmin, 4, S.C.cfl, a.dt_bits)
+    // ... and the gas fluid's limit of the same zones
+    if constexpr (DUST) if (a.finish) BLOCK_MIN_TO_DT(t, ldt_gas, S.wmin, 4, S.C.cfl_gas, a.dt_bits)
   }
 }
 

@@ -23,6 +23,7 @@
 #include "diffusion_device.hpp"
 #include "sources_device.hpp"
 #include "fused_device.hpp"
+#include "march_device.hpp"
 #include <type_traits>
 
 // -DVS_PROF (development builds only: ARTEMIS_HIPFLAGS_KERNELS_DIFFUSION=-DVS_PROF): per-phase shader-clock sums of the
@@ -523,12 +524,7 @@ __global__ __launch_bounds__(256, VS_OCC) void viscous_source_kernel(const PackV
   __shared__ T L;
   __shared__ GeoTabs<QX, QY> GT;
   const int t = threadIdx.x, tx = t % VTX, ty = t / VTX;
-  int id = blockIdx.x;
-  { // workgroup ids are dealt round-robin over the 8 XCDs: give each XCD's L2 one contiguous run of tiles (the halo
-    // columns and the 128-byte lines a row segment straddles are then fetched from HBM once, not once per XCD)
-    const int n = static_cast<int>(gridDim.x), q = n >> 3, rem = n & 7, xcd = id & 7;
-    id = xcd * q + min(xcd, rem) + (id >> 3);
-  }
+  int id = fused::xcd_dealt_id(); // (each XCD's L2 sees one contiguous run of tiles)
   const int ti = id % a.nti;
   id /= a.nti;
   const int tj = id % a.ntj;

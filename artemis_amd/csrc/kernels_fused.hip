@@ -33,6 +33,7 @@
 #include "fused_device.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "march_device.hpp"
 #include "options.hpp"
 #include "pack_view.hpp"
 #include "sources_device.hpp"
@@ -128,8 +129,6 @@ static_assert(sizeof(LdsTile) <= (FTY == 8 ? 80 : 160) * 1024, "LDS budget: two 
 
 using namespace fused;
 
-#define FOR6(X) X(d) X(v1) X(v2) X(v3) X(p) X(e)
-
 struct Ctx { // per-thread constants of the march
   int tx, ty, t, b, i0, j0;
   bool active, multi_d, three_d;
@@ -209,18 +208,7 @@ ADEV void put6(double (*A)[QY][QX], int r, int c, const Cell6 &q) {
   A[0][r][c] = q.d, A[1][r][c] = q.v1, A[2][r][c] = q.v2;
   A[3][r][c] = q.v3, A[4][r][c] = q.p, A[5][r][c] = q.e;
 }
-#define GET6(dst, A, ...)                                                                  \
-  dst.d = A[0] __VA_ARGS__, dst.v1 = A[1] __VA_ARGS__, dst.v2 = A[2] __VA_ARGS__,          \
-  dst.v3 = A[3] __VA_ARGS__, dst.p = A[4] __VA_ARGS__, dst.e = A[5] __VA_ARGS__
-#define PUT8(A, fl, ...)                                                                   \
-  A[0] __VA_ARGS__ = fl.d, A[1] __VA_ARGS__ = fl.m1, A[2] __VA_ARGS__ = fl.m2,             \
-  A[3] __VA_ARGS__ = fl.m3, A[4] __VA_ARGS__ = fl.e, A[5] __VA_ARGS__ = fl.eg,             \
-  A[6] __VA_ARGS__ = fl.pf, A[7] __VA_ARGS__ = fl.vf
-#define GET8(fl, A, ...)                                                                   \
-  fl.d = A[0] __VA_ARGS__, fl.m1 = A[1] __VA_ARGS__, fl.m2 = A[2] __VA_ARGS__,             \
-  fl.m3 = A[3] __VA_ARGS__, fl.e = A[4] __VA_ARGS__, fl.eg = A[5] __VA_ARGS__,             \
-  fl.pf = A[6] __VA_ARGS__, fl.vf = A[7] __VA_ARGS__
-
+// (GET6 / PUT8 / GET8, FOR6: march_device.hpp)
 
 // Stage one plane's primitives (own cell + this thread's halo cell) into S.Q.
 template <class TILE>
@@ -396,47 +384,42 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   // solves and requests its states there: ahead of them it holds both left states through a third solver pass and the
   // stage-2 kernels spill (48 - 64 bytes of scratch with all three of HLLC, HLLE, LLF).
   Cell6 L, L2;
-  GET6(L, S.UPX, [ty][tx]);
+  GET6(6, L, S.UPX, [ty][tx]);
   L2 = L;
-  if (multi_d) { GET6(L2, S.UPY, [ty][tx]); }
+  if (multi_d) { GET6(6, L2, S.UPY, [ty][tx]); }
   fx_lo = solve_face<RIEMANN, 1, SKF>(x.gk, L, lox, fastp);
   if constexpr (CURV) fx_lo.m2 *= gx.h1[1], fx_lo.m3 *= gx.h1[2]; // ScaleMomentumFlux (h1 == 1)
-  if (tx > 0) { PUT8(S.FX, fx_lo, [ty][tx - 1]); }
+  if (tx > 0) { PUT8(6, S.FX, fx_lo, [ty][tx - 1]); }
   fy_lo = fx_lo;
   if (multi_d) {
     fy_lo = solve_face<RIEMANN, 2, SKF>(x.gk, L2, loy, fastp);
     if constexpr (CURV) fy_lo.m2 *= gx.h2[1], fy_lo.m3 *= gx.h2[2];
-    if (ty > 0) { PUT8(S.FY, fy_lo, [ty - 1][tx]); }
+    if (ty > 0) { PUT8(6, S.FY, fy_lo, [ty - 1][tx]); }
   }
   if (t >= 64 && t < 128) { // lanes 0..7: x1 face i0+32 per row; lanes 32..63: x2 face j0+8
-    // ONE Riemann pass for both kinds of perimeter face: the x2 lanes hand the solver their states with the velocity
-    // components rotated (v2, v3, v1) -- which is what solve_face<.., 2> does internally (hllc.hpp:67-69) -- and rotate
-    // the momentum fluxes back, so the duty wave runs three solver passes per plane instead of four (same bits).
+    // ONE Riemann pass for both kinds of perimeter face (march_device.hpp rotate_x2_in / _out), so the duty wave runs
+    // three solver passes per plane instead of four (same bits).
     const int u = t - 64;
     const bool isx = (u < FTY), isy = multi_d && (u >= 32);
     if (isx || isy) {
       const int cx = u - 32;
       Cell6 l, r;
       if (isx) {
-        GET6(l, S.UPX, [u][FTX]);
-        GET6(r, S.LOX, [u]);
+        GET6(6, l, S.UPX, [u][FTX]);
+        GET6(6, r, S.LOX, [u]);
       } else {
-        GET6(l, S.UPY, [FTY][cx]);
-        GET6(r, S.LOY, [cx]);
-        double a_ = l.v1;
-        l.v1 = l.v2, l.v2 = l.v3, l.v3 = a_;
-        a_ = r.v1;
-        r.v1 = r.v2, r.v2 = r.v3, r.v3 = a_;
+        GET6(6, l, S.UPY, [FTY][cx]);
+        GET6(6, r, S.LOY, [cx]);
+        rotate_x2_in(l), rotate_x2_in(r);
       }
       Flux8 fe_ = solve_face<RIEMANN, 1, SKF>(x.gk, l, r, fastp);
       if (isx) {
         if constexpr (CURV) fe_.m2 *= S.HF1[u][0], fe_.m3 *= S.HF1[u][1]; // the face below cell (j0+u, i0+32)
-        PUT8(S.FX, fe_, [u][FTX - 1]);
+        PUT8(6, S.FX, fe_, [u][FTX - 1]);
       } else {
-        const double n_ = fe_.m1; // (normal, t1, t2) = (m2, m3, m1) of the block's frame
-        fe_.m1 = fe_.m3, fe_.m3 = fe_.m2, fe_.m2 = n_;
+        rotate_x2_out(fe_);
         if constexpr (CURV) fe_.m2 *= S.HF2[cx][0], fe_.m3 *= S.HF2[cx][1]; // the face below cell (j0+8, i0+cx)
-        PUT8(S.FY, fe_, [FTY - 1][cx]);
+        PUT8(6, S.FY, fe_, [FTY - 1][cx]);
       }
     }
   }
@@ -479,14 +462,14 @@ ADEV void plane_store_fluxes(TILE &S, const PackView &P, const Ctx &x, const int
   put(0, fx_lo, c);
   if (x.i0 + tx == P.ie) {
     Flux8 hi;
-    GET8(hi, S.FX, [ty][tx]);
+    GET8(6, hi, S.FX, [ty][tx]);
     put(0, hi, c + 1);
   }
   if (multi_d) {
     put(1, fy_lo, c);
     if (x.j0 + ty == P.je) {
       Flux8 hi;
-      GET8(hi, S.FY, [ty][tx]);
+      GET8(6, hi, S.FY, [ty][tx]);
       put(1, hi, c + x.sj);
     }
   }
@@ -518,8 +501,8 @@ ADEV void plane_update(TILE &S, const PackView &P, const StageK &a, const Ctx &x
   const double gm1 = x.gm1;
   const FluidView &f = P.gas;
   Flux8 fx_hi, fy_hi = fx_lo;
-  GET8(fx_hi, S.FX, [ty][tx]);
-  if (multi_d) { GET8(fy_hi, S.FY, [ty][tx]); }
+  GET8(6, fx_hi, S.FX, [ty][tx]);
+  if (multi_d) { GET8(6, fy_hi, S.FY, [ty][tx]); }
   if (!x.active) return;
   const double *g = x.g + opaque(4); // (scalar loads at their use: fused_device.hpp kload)
   const double dx1 = x.dx1, dx2 = x.dx2;
@@ -571,7 +554,9 @@ ADEV void plane_update(TILE &S, const PackView &P, const StageK &a, const Ctx &x
     G -= bdt_vol * 0.5 * (fz_lo.pf + fz_hi.pf) * (ax3 * fz_hi.vf - ax3 * fz_lo.vf);
   }
   // SetAuxillaryFields (fill_derived.cpp:54-73, artemis_utils.hpp:43-62) and ConsToPrim
-  // (fill_derived.cpp:137-151) divide six times by the same floored density.
+  // (fill_derived.cpp:137-151) divide six times by the same floored density.  Not plane_update_curv's form: every
+  // scale factor is 1, so one reciprocal serves all six divisions, and the redo list takes the zones whose momenta
+  // would need the IEEE fallback -- another expression set.
   const double w_d = (D > f.dfloor) ? D : f.dfloor; // == max(D, dfloor) of artemis_utils.hpp:49
   const Recip rd = recip(w_d);
   {
@@ -662,9 +647,9 @@ ADEV void plane_update_curv(TILE &S, const PackView &P, const StageK &a, const S
   const bool multi_d = D3 || x.multi_d;
   constexpr bool three_d = D3;
   Flux8 fx_hi, fy_hi, fy_lo = fy_lo_in, fz_lo = fz_lo_in, fz_hi = fz_hi_in;
-  GET8(fx_hi, S.FX, [ty][tx]);
+  GET8(6, fx_hi, S.FX, [ty][tx]);
   fy_hi = fx_hi;
-  if (multi_d) { GET8(fy_hi, S.FY, [ty][tx]); }
+  if (multi_d) { GET8(6, fy_hi, S.FY, [ty][tx]); }
   if (!x.active) return;
   const FluidView &f = P.gas;
   const int b = x.b;
@@ -781,14 +766,8 @@ ADEV void plane_update_curv(TILE &S, const PackView &P, const StageK &a, const S
   gst(a.prim_out[b * 6 + 3], c, n3);
   gst(a.prim_out[b * 6 + 4], c, amax(0.0, x.gm1 * w_d * w_s)); // fill_derived.cpp:247 (consumers recompute it anyway)
   gst(a.prim_out[b * 6 + 5], c, w_s);
-  if constexpr (WITH_DT) { // Gas::EstimateTimestepMesh on the new state (gas.cpp:411-433)
-    const double bulk = (x.gm1 + 1.0) * x.gm1 * w_d * w_s;
-    const double cs = sqrt_pos(div(bulk, rwd));
-    double denom = div(fabs(n1) + cs, co.width1());
-    if (multi_d) denom += div(fabs(n2) + cs, co.width2());
-    if (three_d) denom += div(fabs(n3) + cs, co.width3());
-    ldt = amin(ldt, div(1.0, denom));
-  }
+  // Gas::EstimateTimestepMesh on the new state
+  if constexpr (WITH_DT) ldt = amin(ldt, zone_dt_term(w_d, n1, n2, n3, w_s, rwd, x.gm1, co, multi_d, three_d));
 }
 
 template <int RIEMANN, int RECON, bool HAS_U1, bool WRITE_CONS, bool WITH_DT, bool D3, bool CURV = false, bool FLUXES = false>
@@ -989,18 +968,18 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
       if constexpr (CURV && RECON == 1) {
         const PlmGeo g3 = plm_geo_x3(gx.co, x.g, k0 - 1);
         double unused_;
-#define ZL0(m) plm_g_shared<0>(qmm.m, qc.m, qn.m, zl.m, unused_, g3);
+#define ZL0(m, n) plm_g_shared<0>(qmm.m, qc.m, qn.m, zl.m, unused_, g3);
         FOR6(ZL0)
 #undef ZL0
       } else {
         const bool f0 = !(FLUXES && __any(tiny_v(qmm) || tiny_v(qc) || tiny_v(qn)));
         bool flat_ = false;
         if constexpr (SK6) {
-#define ZF0(m) &&plm_flat(qmm.m, qc.m, qn.m)
+#define ZF0(m, n) &&plm_flat(qmm.m, qc.m, qn.m)
           flat_ = f0 && __all(true FOR6(ZF0));
 #undef ZF0
         }
-#define ZL0(m) zl.m = up_val<RECON>(qc.m, flat_ ? 0.0 : slope_sel<RECON, SK1>(qmm.m, qc.m, qn.m, f0));
+#define ZL0(m, n) zl.m = up_val<RECON>(qc.m, flat_ ? 0.0 : slope_sel<RECON, SK1>(qmm.m, qc.m, qn.m, f0));
         FOR6(ZL0)
 #undef ZL0
       }
@@ -1062,11 +1041,11 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
                            tiny_nonzero(qn.v2) || tiny_nonzero(qn.v3) || tiny_nonzero(qnn.v1) || tiny_nonzero(qnn.v2) ||
                            tiny_nonzero(qnn.v3);
         if (!__any(tiny3)) {
-#define ZSL(m) plm_g_shared<2>(qc.m, qn.m, qnn.m, zl_next.m, zr.m, g3);
+#define ZSL(m, n) plm_g_shared<2>(qc.m, qn.m, qnn.m, zl_next.m, zr.m, g3);
           FOR6(ZSL)
 #undef ZSL
         } else {
-#define ZSL(m) plm_g_shared<0>(qc.m, qn.m, qnn.m, zl_next.m, zr.m, g3);
+#define ZSL(m, n) plm_g_shared<0>(qc.m, qn.m, qnn.m, zl_next.m, zr.m, g3);
           FOR6(ZSL)
 #undef ZSL
         }
@@ -1079,7 +1058,7 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
   }
 #define ZSL6(F) ZSL(d, F) ZSL(v1, F) ZSL(v2, F) ZSL(v3, F) ZSL(p, F) ZSL(e, F)
         if constexpr (SK6) {
-#define ZF(m) &&plm_flat(qc.m, qn.m, qnn.m)
+#define ZF(m, n) &&plm_flat(qc.m, qn.m, qnn.m)
           if (fast_col && __all(true FOR6(ZF))) { ZSL6(true) } else { ZSL6(false) }
 #undef ZF
         } else {
@@ -1111,17 +1090,7 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
     for (int q = 0; q < 10; ++q) atomicAdd(&g_fused_prof[q], prof_acc[q]);
 #endif
   if constexpr (WITH_DT) {
-    __syncthreads(); // LOX is reused as reduction scratch
-    for (int off = 32; off > 0; off >>= 1) ldt = fmin(ldt, __shfl_down(ldt, off, 64));
-    double *wmin = &S.LOX[0][0];
-    if ((x.t & 63) == 0) wmin[x.t >> 6] = ldt;
-    __syncthreads();
-    if (x.t == 0) {
-      double m = wmin[0];
-      for (int w = 1; w < NW; ++w) m = fmin(m, wmin[w]);
-      if (m < DBL_MAX)
-        atomicMin(a.dt_bits, static_cast<unsigned long long>(__double_as_longlong(a.cfl * m)));
-    }
+    BLOCK_MIN_TO_DT(x.t, ldt, (&S.LOX[0][0]), NW, a.cfl, a.dt_bits) // LOX is reused as reduction scratch
   }
   if (shell_wg) {
     // MI355X: per-CU L1 and per-XCD L2 are not coherent across CUs/XCDs.  Every wave drains its
@@ -1220,7 +1189,7 @@ __global__ __launch_bounds__(256) void stage_redo_kernel(const PackView P, const
         w[m] = load_cell(qr, q1, q2, q3, qe, cm, P.gm1);
       }
       Cell6 Ll, Rl, Lu, Ru;
-#define RD(v)                                                                                          \
+#define RD(v, n)                                                                                        \
   {                                                                                                    \
     double sm = 0.0, sc = 0.0, sp = 0.0;                                                               \
     if constexpr (RECON == 1) sm = plm_dqm(w[0].v, w[1].v, w[2].v), sc = plm_dqm(w[1].v, w[2].v, w[3].v), sp = plm_dqm(w[2].v, w[3].v, w[4].v); \

@@ -5,7 +5,8 @@
 // The caller has filled every ghost zone (the general stage's plain contract); the pressure slot of the output is not
 // written, exactly like the cell-centred kernel (variant 0) this march replaces for such packs.
 //
-// Shape: the 2.5-D tile march of kernels_fused.hip / kernels_curv.hip with the stencil radius of PPM.
+// Shape: the 2.5-D tile march of kernels_fused.hip / kernels_curv.hip with the stencil radius of PPM; what the marches
+// have in common is in march_device.hpp.
 //   * a 256-thread workgroup owns a 32 x 8 column of zones and marches along x3 through a chunk of planes;
 //   * x3 in registers: a thread keeps its own column's planes k-1 .. k+2, fetches plane k+3 at the top of a trip, forms
 //     the two x3 face values of zone k+1 from those five and carries the upper one to the next trip, so every x3 face
@@ -33,6 +34,7 @@
 #include "fused_device.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "march_device.hpp"
 #include "options.hpp"
 #include "pack_view.hpp"
 #include "sources_device.hpp"
@@ -80,22 +82,6 @@ struct PpmTile {
 };
 static_assert(sizeof(PpmTile) <= 80 * 1024, "two workgroups per CU (160 KiB of LDS)");
 
-#define PFOR6(X) X(d, 0) X(v1, 1) X(v2, 2) X(v3, 3) X(p, 4) X(e, 5)
-// ... with a scheduling fence after the third variable: three reconstruction chains interleave (six would need the
-// registers of twelve more doubles)
-#define PFOR6_33(X) X(d, 0) X(v1, 1) X(v2, 2) __builtin_amdgcn_sched_barrier(0); X(v3, 3) X(p, 4) X(e, 5)
-#define PGET6(dst, A, ...)                                                                 \
-  dst.d = A[0] __VA_ARGS__, dst.v1 = A[1] __VA_ARGS__, dst.v2 = A[2] __VA_ARGS__,          \
-  dst.v3 = A[3] __VA_ARGS__, dst.p = A[4] __VA_ARGS__, dst.e = A[5] __VA_ARGS__
-#define PPUT8(A, fl, ...)                                                                  \
-  A[0] __VA_ARGS__ = fl.d, A[1] __VA_ARGS__ = fl.m1, A[2] __VA_ARGS__ = fl.m2,             \
-  A[3] __VA_ARGS__ = fl.m3, A[4] __VA_ARGS__ = fl.e, A[5] __VA_ARGS__ = fl.eg,             \
-  A[6] __VA_ARGS__ = fl.pf, A[7] __VA_ARGS__ = fl.vf
-#define PGET8(fl, A, ...)                                                                  \
-  fl.d = A[0] __VA_ARGS__, fl.m1 = A[1] __VA_ARGS__, fl.m2 = A[2] __VA_ARGS__,             \
-  fl.m3 = A[3] __VA_ARGS__, fl.e = A[4] __VA_ARGS__, fl.eg = A[5] __VA_ARGS__,             \
-  fl.pf = A[6] __VA_ARGS__, fl.vf = A[7] __VA_ARGS__
-
 // the two face values of a zone from its five-zone stencil: shared-reciprocal PPM4 (FAST) or ppm4 as it stands
 template <bool FAST>
 ADEV void faces5(double qmm, double qm, double q, double qp, double qpp, const Recip &r12, double &up, double &lo) {
@@ -107,11 +93,7 @@ template <int RIEMANN>
 __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, const PpmK a) {
   __shared__ PpmTile S;
   const int t = threadIdx.x, tx = t % FTX, ty = t / FTX;
-  int id = blockIdx.x;
-  { // ids dealt so that each XCD's L2 sees one run of tiles (kernels_curv.hip)
-    const int n = static_cast<int>(gridDim.x), q = n >> 3, rem = n & 7, xcd = id & 7;
-    id = xcd * q + min(xcd, rem) + (id >> 3);
-  }
+  int id = xcd_dealt_id();
   const int ti = id % a.nti;
   id /= a.nti;
   const int tj = id % a.ntj;
@@ -153,11 +135,7 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
     const int u = t - 2 * FH * FTX, cc = u % (2 * FH);
     hr = u / (2 * FH) + FH, hc = (cc < FH) ? cc : FTX + cc;
   }
-  unsigned hcol = col; // (threads without a halo duty: their own column)
-  if (hr >= 0) {
-    const int gi = min(max(i0 - FH + hc, 0), P.ni - 1), gj = min(max(j0 - FH + hr, 0), P.nj - 1);
-    hcol = static_cast<unsigned>(gj) * sj + static_cast<unsigned>(gi);
-  }
+  const unsigned hcol = halo_column<FH>(hr, hc, i0, j0, P.ni, P.nj, sj, col);
   // cell widths (device_math.hpp cell_geom: the reference's BBox arithmetic); x1 / x2 are constants of the march
   const double dx1 = (g[0] + (i + 1) * g[1]) - (g[0] + i * g[1]);
   const double dx2 = (g[2] + (j + 1) * g[3]) - (g[2] + j * g[3]);
@@ -195,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
     L.m = lane_below(up_);                                                                                      \
     if (tx == FTX - 1) S.UPXE[n][ty] = up_;                                                                     \
   }
-    PFOR6_33(SLX)
+    FOR6_33(SLX)
 #undef SLX
     __builtin_amdgcn_sched_barrier(0);
 #define SLY(m, n)                                                                                               \
@@ -205,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
                   S.Q[n][ty + FH + 1][tx + FH], S.Q[n][ty + FH + 2][tx + FH], r12, up_, loy.m);                 \
     S.UPY[n][ty + 1][tx] = up_;                                                                                 \
   }
-    PFOR6_33(SLY)
+    FOR6_33(SLY)
 #undef SLY
     if (duty >= 128 && duty < 128 + 2 * FTY) { // columns i0-1 (upper value) and i0+FTX (lower value)
       const int u = duty - 128, row = u >> 1, side = u & 1;
@@ -246,32 +224,28 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
         const int cx = u - 32;
         Cell6 l, r;
         if (isx) {
-          PGET6(l, S.UPXE, [u]);
-          PGET6(r, S.LOXE, [u]);
+          GET6(6, l, S.UPXE, [u]);
+          GET6(6, r, S.LOXE, [u]);
         } else {
-          PGET6(l, S.UPY, [FTY][cx]);
-          PGET6(r, S.LOY, [cx]);
-          double a_ = l.v1;
-          l.v1 = l.v2, l.v2 = l.v3, l.v3 = a_;
-          a_ = r.v1;
-          r.v1 = r.v2, r.v2 = r.v3, r.v3 = a_;
+          GET6(6, l, S.UPY, [FTY][cx]);
+          GET6(6, r, S.LOY, [cx]);
+          rotate_x2_in(l), rotate_x2_in(r);
         }
         Flux8 fe_ = solve_face<RIEMANN, 1>(gk, l, r, fastp);
         if (isx) {
-          PPUT8(S.FXE, fe_, [u]);
+          PUT8(6, S.FXE, fe_, [u]);
         } else {
-          const double n_ = fe_.m1; // (normal, t1, t2) = (m2, m3, m1) of the block's frame
-          fe_.m1 = fe_.m3, fe_.m3 = fe_.m2, fe_.m2 = n_;
-          PPUT8(S.FY, fe_, [FTY - 1][cx]);
+          rotate_x2_out(fe_);
+          PUT8(6, S.FY, fe_, [FTY - 1][cx]);
         }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (tx == 0) { PGET6(L, S.UPX0, [ty]); }
+    if (tx == 0) { GET6(6, L, S.UPX0, [ty]); }
     fx_lo = solve_face<RIEMANN, 1>(gk, L, lox, fastp);
-    PGET6(L, S.UPY, [ty][tx]);
+    GET6(6, L, S.UPY, [ty][tx]);
     fy_lo = solve_face<RIEMANN, 2>(gk, L, loy, fastp);
-    if (ty > 0) { PPUT8(S.FY, fy_lo, [ty - 1][tx]); }
+    if (ty > 0) { PUT8(6, S.FY, fy_lo, [ty - 1][tx]); }
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
   };
@@ -283,11 +257,9 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
   };
   // after the second barrier: the upper x1 / x2 faces from the neighbours
   auto upper12 = [&](const Flux8 &fx_lo, Flux8 &fx_hi, Flux8 &fy_hi) {
-    fx_hi.d = lane_above(fx_lo.d), fx_hi.m1 = lane_above(fx_lo.m1), fx_hi.m2 = lane_above(fx_lo.m2);
-    fx_hi.m3 = lane_above(fx_lo.m3), fx_hi.e = lane_above(fx_lo.e), fx_hi.eg = lane_above(fx_lo.eg);
-    fx_hi.pf = lane_above(fx_lo.pf), fx_hi.vf = lane_above(fx_lo.vf);
-    if (tx == FTX - 1) { PGET8(fx_hi, S.FXE, [ty]); }
-    PGET8(fy_hi, S.FY, [ty][tx]);
+    flux_from_lane_above<6>(fx_lo, fx_hi);
+    if (tx == FTX - 1) { GET8(6, fx_hi, S.FXE, [ty]); }
+    GET8(6, fy_hi, S.FY, [ty][tx]);
   };
 
   // ---- the update of zone (k, j, i) from the folded sums (kernels_stage_cell.hip's gas branch on a Cartesian block)
@@ -337,7 +309,9 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
     u0.eg -= s.te[1];
     u0.m3 += s.tm[2];
     u0.eg -= s.te[2];
-    // ---- SetAuxillaryFields (fill_derived.cpp:58-71) + ConsToPrim (:132-146); every scale factor is 1
+    // ---- SetAuxillaryFields (fill_derived.cpp:58-71) + ConsToPrim (:132-146); every scale factor is 1.  Not
+    // the curvilinear marches' form (kernels_curv.hip update): with hx == 1 the two floored densities are one, so ONE
+    // reciprocal serves all six divisions and there is no division by a scale factor -- another expression set
     const double w_d = (u0.d > KC.dfloor) ? u0.d : KC.dfloor;
     const Recip rwd = recip(w_d);
     const bool tiny_m = __any(tiny_nonzero(u0.m1) || tiny_nonzero(u0.m2) || tiny_nonzero(u0.m3));
@@ -382,10 +356,10 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
     const Cell6 c4 = finish_cell(w3, gm1);
     double unused_;
 #define ZL0(m, n) ppm4(c0.m, c1.m, c2.m, c3.m, c4.m, zl.m, unused_);
-    PFOR6(ZL0)
+    FOR6(ZL0)
 #undef ZL0
 #define ZPUT(m, n) S.ZL[n][t] = zl.m;
-    PFOR6(ZPUT)
+    FOR6(ZPUT)
     S.WM[0][t] = w0.d, S.WM[1][t] = w0.v1, S.WM[2][t] = w0.v2, S.WM[3][t] = w0.v3, S.WM[4][t] = w0.e;
     tb = (tiny_r(wm) ? 16u : 0u) | (tiny_r(w0) ? 8u : 0u) | (tiny_r(w1) ? 4u : 0u) | (tiny_r(w2) ? 2u : 0u) | (tiny_r(w3) ? 1u : 0u);
   }
@@ -427,15 +401,15 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
       const Cell6 c0 = finish_cell(w0, gm1), c2 = finish_cell(w2, gm1), c3 = finish_cell(w3, gm1), c4 = finish_cell(w4, gm1);
       if (fast3) {
 #define ZSL(m, n) ppm4_fast(c0.m, qc.m, c2.m, c3.m, c4.m, r12, zl_next.m, zr.m);
-        PFOR6_33(ZSL)
+        FOR6_33(ZSL)
 #undef ZSL
       } else {
 #define ZSL(m, n) ppm4(c0.m, qc.m, c2.m, c3.m, c4.m, zl_next.m, zr.m);
-        PFOR6_33(ZSL)
+        FOR6_33(ZSL)
 #undef ZSL
       }
 #define ZGET(m, n) zl.m = S.ZL[n][t]; // (written by this thread in the previous trip: no barrier needed)
-      PFOR6(ZGET)
+      FOR6(ZGET)
 #undef ZGET
       S.ZL[0][t] = zl_next.d, S.ZL[1][t] = zl_next.v1, S.ZL[2][t] = zl_next.v2;
       S.ZL[3][t] = zl_next.v3, S.ZL[4][t] = zl_next.p, S.ZL[5][t] = zl_next.e;
@@ -452,17 +426,7 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
     w1 = w2, w2 = w3, w3 = w4;
   }
 #undef ZPUT
-  if (a.dt_bits) {
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) ldt = fmin(ldt, __shfl_down(ldt, off, 64));
-    if ((t & 63) == 0) S.wmin[t >> 6] = ldt;
-    __syncthreads();
-    if (t == 0) {
-      double m = S.wmin[0];
-      for (int w = 1; w < 4; ++w) m = fmin(m, S.wmin[w]);
-      if (m < DBL_MAX) atomicMin(a.dt_bits, static_cast<unsigned long long>(__double_as_longlong(S.C.cfl * m)));
-    }
-  }
+  if (a.dt_bits) BLOCK_MIN_TO_DT(t, ldt, S.wmin, 4, S.C.cfl, a.dt_bits)
 }
 } // namespace
 
