@@ -104,6 +104,34 @@ int validate_registers(const artemis_pack_t *p, const char *task) {
       return fail(ARTEMIS_HIP_EINVAL, "%s needs the cons0 (u0) and cons1 (u1) tables of every fluid in the pack", task);
   return 0;
 }
+// Guards the stage entry points share (general stage, stage epilogue, refined-mesh fix-up); each keeps its own sequence
+int stage_gravity_guard(const artemis_pack_t *p, const artemis_gravity_t *g, bool type_only = false) {
+  if (!artemis::gravity_type_carried(g)) return fail(ARTEMIS_HIP_EUNSUPPORTED, "gravity type %d (nbody) is not built", g->type);
+  if (!g || type_only) return 0;
+  if (g->type == ARTEMIS_GRAVITY_BINARY &&
+      (p->coords == ARTEMIS_AXISYMMETRIC || p->coords == ARTEMIS_SPHERICAL1D || p->coords == ARTEMIS_SPHERICAL2D))
+    return fail(ARTEMIS_HIP_EINVAL, "Binary gravity is not compatable with axisymmetric coordinates!");
+  if (g->type != ARTEMIS_GRAVITY_UNIFORM && p->coords == ARTEMIS_CYLINDRICAL && !p->metric)
+    return fail(ARTEMIS_HIP_EINVAL, "point-mass gravity on cylindrical blocks needs the metric tables");
+  return 0;
+}
+int stage_qshear_guard(const artemis_pack_t *p, const artemis_stage_general_args_t *a) { // rotating_frame.cpp:34-38
+  if (a->rf_omega != 0.0 && p->coords != ARTEMIS_CARTESIAN && a->rf_qshear != 0.0)
+    return fail(ARTEMIS_HIP_EINVAL, "rotating_frame/qshear must be zero for non-Cartesian coordinate systems!");
+  return 0;
+}
+int stage_cooling_guard(const artemis_pack_t *p, const artemis_cooling_t *c, bool with_cv) {
+  if (!c) return 0;
+  if (p->gas.nspecies && (!c->tref || !c->beta))
+    return fail(ARTEMIS_HIP_EINVAL, "cooling: tref / beta tables are required (artemis_hip_cooling_table_fill)");
+  if (with_cv && !(c->cv > 0.0)) return fail(ARTEMIS_HIP_EINVAL, "cooling: specific heat cv must be positive");
+  return 0;
+}
+int stage_cons0_guard(const artemis_pack_t *p, const artemis_stage_general_args_t *a, const char *prefix) {
+  if (a->defer_finish && ((p->gas.nspecies && !p->gas.cons0) || (p->dust.nspecies && !p->dust.cons0)))
+    return fail(ARTEMIS_HIP_EINVAL, "%s: cons0 tables are required", prefix);
+  return 0;
+}
 inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
 int after_launch(const char *what) { return check_hip(hipGetLastError(), what); }
 
@@ -648,8 +676,7 @@ static int validate_ml_fix(const artemis_pack_t *p, const artemis_stage_general_
     return fail(ARTEMIS_HIP_EUNSUPPORTED, "refined-mesh fix-up: drag couples the fluids after the update: set defer_finish and run "
                                           "artemis_hip_stage_finish after the fix-up");
   if (int rc = validate_stage_nbody(p, a)) return rc;
-  if (a->defer_finish && ((p->gas.nspecies && !p->gas.cons0) || (p->dust.nspecies && !p->dust.cons0)))
-    return fail(ARTEMIS_HIP_EINVAL, "defer_finish: cons0 tables are required");
+  if (int rc = stage_cons0_guard(p, a, "defer_finish")) return rc;
   if (p->gas.nspecies && (!a->gas_in || !a->gas_u1 || !a->gas_out))
     return fail(ARTEMIS_HIP_EINVAL, "refined-mesh fix-up: gas_in / gas_u1 / gas_out are required");
   if (p->dust.nspecies && (!a->dust_in || !a->dust_u1 || !a->dust_out))
@@ -672,15 +699,10 @@ int artemis_hip_ml_stage_fixup(const artemis_pack_t *p, const artemis_stage_gene
                                const artemis_ml_fix_cell_t *cells_dev, int ncells, void *stream) {
   if (int rc = validate_ml_fix(p, a)) return rc;
   if (ncells < 0 || (ncells > 0 && !cells_dev)) return fail(ARTEMIS_HIP_EINVAL, "multilevel: bad zone list");
-  if (a->gravity) {
-    const artemis_gravity_t *g = a->gravity;
-    if (g->type != ARTEMIS_GRAVITY_UNIFORM && g->type != ARTEMIS_GRAVITY_POINT && g->type != ARTEMIS_GRAVITY_BINARY)
-      return fail(ARTEMIS_HIP_EUNSUPPORTED, "gravity type %d (nbody) is not built", g->type);
-  }
+  if (int rc = stage_gravity_guard(p, a->gravity, true)) return rc;
   if (a->diffusion)
     if (int rc = validate_diffusion(p, a->diffusion, true)) return rc;
-  if (a->cooling && p->gas.nspecies && (!a->cooling->tref || !a->cooling->beta))
-    return fail(ARTEMIS_HIP_EINVAL, "cooling: tref / beta tables are required (artemis_hip_cooling_table_fill)");
+  if (int rc = stage_cooling_guard(p, a->cooling, false)) return rc;
   artemis::launch_ml_stage_fixup(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon,
                                  p->dust.riemann, cells_dev, ncells, S(stream));
   return after_launch("ml_stage_fixup");
@@ -894,6 +916,9 @@ int artemis_hip_timestep_all(const artemis_pack_t *p, double cfl_gas, double cfl
   return after_launch("EstimateTimestepMesh (all limits)");
 }
 
+static artemis::StagePlan stage_plan_of(const artemis_pack_t *p, const artemis_stage_general_args_t *a) {
+  return artemis::plan_stage_general(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon, p->dust.riemann);
+}
 int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_general_args_t *a,
                               void *stream) {
   if (int rc = validate(p)) return rc;
@@ -907,30 +932,16 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
     return fail(ARTEMIS_HIP_EINVAL, "general stage: dust_in / dust_u1 / dust_out are required");
   if ((p->gas.nspecies && a->gas_in == a->gas_out) || (p->dust.nspecies && a->dust_in == a->dust_out))
     return fail(ARTEMIS_HIP_EINVAL, "general stage: *_out must not alias *_in");
-  if (a->gravity) { // same guards as artemis_hip_external_gravity
-    const artemis_gravity_t *g = a->gravity;
-    if (g->type != ARTEMIS_GRAVITY_UNIFORM && g->type != ARTEMIS_GRAVITY_POINT && g->type != ARTEMIS_GRAVITY_BINARY)
-      return fail(ARTEMIS_HIP_EUNSUPPORTED, "gravity type %d (nbody) is not built", g->type);
-    if (g->type == ARTEMIS_GRAVITY_BINARY &&
-        (p->coords == ARTEMIS_AXISYMMETRIC || p->coords == ARTEMIS_SPHERICAL1D || p->coords == ARTEMIS_SPHERICAL2D))
-      return fail(ARTEMIS_HIP_EINVAL, "Binary gravity is not compatable with axisymmetric coordinates!");
-    if (g->type != ARTEMIS_GRAVITY_UNIFORM && p->coords == ARTEMIS_CYLINDRICAL && !p->metric)
-      return fail(ARTEMIS_HIP_EINVAL, "point-mass gravity on cylindrical blocks needs the metric tables");
-  }
-  if (a->rf_omega != 0.0 && p->coords != ARTEMIS_CARTESIAN && a->rf_qshear != 0.0) // rotating_frame.cpp:34-38
-    return fail(ARTEMIS_HIP_EINVAL, "rotating_frame/qshear must be zero for non-Cartesian coordinate systems!");
+  if (int rc = stage_gravity_guard(p, a->gravity)) return rc;
+  if (int rc = stage_qshear_guard(p, a)) return rc;
   if (int rc = validate_stage_nbody(p, a)) return rc;
   if (a->diffusion) {
     if (int rc = validate_diffusion(p, a->diffusion, a->diffusion_sums == nullptr)) return rc;
     if (a->diffusion_sums && p->gas.nspecies != 1)
       return fail(ARTEMIS_HIP_EINVAL, "general stage: diffusion_sums are for one gas species");
   }
-  if (a->cooling) {
-    if (a->drag) return fail(ARTEMIS_HIP_EUNSUPPORTED, "general stage: cooling together with drag runs on the per-task kernels");
-    if (p->gas.nspecies && (!a->cooling->tref || !a->cooling->beta))
-      return fail(ARTEMIS_HIP_EINVAL, "cooling: tref / beta tables are required (artemis_hip_cooling_table_fill)");
-    if (!(a->cooling->cv > 0.0)) return fail(ARTEMIS_HIP_EINVAL, "cooling: specific heat cv must be positive");
-  }
+  if (a->cooling && a->drag) return fail(ARTEMIS_HIP_EUNSUPPORTED, "general stage: cooling together with drag runs on the per-task kernels");
+  if (int rc = stage_cooling_guard(p, a->cooling, true)) return rc;
   if (a->drag) {
     if (int rc = validate_damp_visc(a->drag)) return rc;
     if (a->drag->type == ARTEMIS_DRAG_SIMPLE_DUST && (p->gas.nspecies < 1 || p->dust.nspecies < 1))
@@ -940,12 +951,10 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
     if ((p->gas.nspecies && !p->gas.cons0) || (p->dust.nspecies && !p->dust.cons0))
       return fail(ARTEMIS_HIP_EINVAL, "general stage with drag: cons0 tables are required as scratch");
   }
-  if (a->defer_finish && ((p->gas.nspecies && !p->gas.cons0) || (p->dust.nspecies && !p->dust.cons0)))
-    return fail(ARTEMIS_HIP_EINVAL, "general stage, defer_finish: cons0 tables are required");
+  if (int rc = stage_cons0_guard(p, a, "general stage, defer_finish")) return rc;
   if (a->defer_finish && a->cooling)
     return fail(ARTEMIS_HIP_EUNSUPPORTED, "general stage: defer_finish with cooling (it follows drag in the task list)");
-  if (a->strat_faces && artemis::stage_general_variant(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon,
-                                                       p->dust.riemann) != 1)
+  if (a->strat_faces && stage_plan_of(p, a).gas != artemis::GasKernel::RowMarch)
     return fail(ARTEMIS_HIP_EUNSUPPORTED, "general stage: strat_faces (conditions inside the kernel) is served by the 2-D row "
                                           "march only, for all four faces of one block (strat_faces = 15)");
   artemis::launch_stage_cell(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann,
@@ -956,16 +965,14 @@ int artemis_hip_stage_general(const artemis_pack_t *p, const artemis_stage_gener
 int artemis_hip_stage_general_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a) {
   if (!p || !a) return 0;
   if (a->defer_finish < 0 || a->defer_finish > 2) return 0; // (artemis_hip_stage_general refuses such a call: EINVAL)
-  return artemis::stage_general_variant(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon,
-                                        p->dust.riemann);
+  return static_cast<int>(stage_plan_of(p, a).gas);
 }
 
 int artemis_hip_stage_general_dust_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a) {
   if (!p || !a) return 0;
   if (p->dust.nspecies == 0) return -1;
   if (a->defer_finish < 0 || a->defer_finish > 2) return 0;
-  return artemis::stage_general_dust_variant(artemis::make_pack_view(*p), *a, p->gas.recon, p->gas.riemann, p->dust.recon,
-                                             p->dust.riemann);
+  return stage_plan_of(p, a).dust_code();
 }
 
 static int stage_epilogue_common(const artemis_pack_t *p, const artemis_stage_general_args_t *a, void *stream, bool to_cons) {
@@ -980,25 +987,11 @@ static int stage_epilogue_common(const artemis_pack_t *p, const artemis_stage_ge
       if (!f->flux[d] || (f == &p->gas && (!f->pflux[d] || !f->vface[d])))
         return fail(ARTEMIS_HIP_EINVAL, "stage epilogue: flux / pflux / vface tables are required");
   }
-  if (a->gravity) {
-    const artemis_gravity_t *g = a->gravity;
-    if (g->type != ARTEMIS_GRAVITY_UNIFORM && g->type != ARTEMIS_GRAVITY_POINT && g->type != ARTEMIS_GRAVITY_BINARY)
-      return fail(ARTEMIS_HIP_EUNSUPPORTED, "gravity type %d (nbody) is not built", g->type);
-    if (g->type == ARTEMIS_GRAVITY_BINARY &&
-        (p->coords == ARTEMIS_AXISYMMETRIC || p->coords == ARTEMIS_SPHERICAL1D || p->coords == ARTEMIS_SPHERICAL2D))
-      return fail(ARTEMIS_HIP_EINVAL, "Binary gravity is not compatable with axisymmetric coordinates!");
-    if (g->type != ARTEMIS_GRAVITY_UNIFORM && p->coords == ARTEMIS_CYLINDRICAL && !p->metric)
-      return fail(ARTEMIS_HIP_EINVAL, "point-mass gravity on cylindrical blocks needs the metric tables");
-  }
-  if (a->rf_omega != 0.0 && p->coords != ARTEMIS_CARTESIAN && a->rf_qshear != 0.0)
-    return fail(ARTEMIS_HIP_EINVAL, "rotating_frame/qshear must be zero for non-Cartesian coordinate systems!");
+  if (int rc = stage_gravity_guard(p, a->gravity)) return rc;
+  if (int rc = stage_qshear_guard(p, a)) return rc;
   if (a->diffusion)
     if (int rc = validate_diffusion(p, a->diffusion, true)) return rc;
-  if (a->cooling) {
-    if (p->gas.nspecies && (!a->cooling->tref || !a->cooling->beta))
-      return fail(ARTEMIS_HIP_EINVAL, "cooling: tref / beta tables are required (artemis_hip_cooling_table_fill)");
-    if (!(a->cooling->cv > 0.0)) return fail(ARTEMIS_HIP_EINVAL, "cooling: specific heat cv must be positive");
-  }
+  if (int rc = stage_cooling_guard(p, a->cooling, true)) return rc;
   if (to_cons && a->cooling) return fail(ARTEMIS_HIP_EUNSUPPORTED, "stage epilogue (cons): cooling acts after drag; use the separate tasks");
   artemis::launch_stage_epilogue(artemis::make_pack_view(*p), *a, S(stream), to_cons);
   return after_launch(to_cons ? "stage_epilogue_cons" : "stage_epilogue");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pack_view.hpp"
+#include "stage_plan.hpp"
 
 namespace artemis {
 void launch_calculate_fluxes(const PackView &P, int fluid, int riemann, int recon, hipStream_t s);
@@ -47,11 +48,9 @@ int launch_stage_fused(const PackView &P, const artemis_stage_args_t &a, int rie
 int launch_stage_fused_redo_shell(const PackView &P, const artemis_stage_args_t &a, int riemann, int recon, hipStream_t s);
 bool fused_flux_covers(const PackView &P, int recon);
 int launch_flux_fused(const PackView &P, int riemann, int recon, hipStream_t s);
-bool fused_curv_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas);
-void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
+void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int riemann_gas,
                              hipStream_t s);
 // kernels_curv.hip
-bool curv_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas);
 // Chunks of an x3 march (kernels_curv.hip, the viscous source): a launch proceeds in rounds of `slots` resident
 // workgroups and a half-empty last round costs a full one; every chunk pays `prime` priming trips (in units of a full
 // trip: measured, a priming trip of the stage march costs about half a trip).  The number of chunks
@@ -70,13 +69,11 @@ inline int pick_march_chunks(int planes, long tiles, long slots, int cmax, doubl
   }
   return best;
 }
-bool curv_march_covers_dust(const PackView &P, const artemis_stage_general_args_t &g, int recon_dust, int riemann_dust);
-// finish (fluid 1 only): the dust march also runs DragSource + SetAuxillaryFields + ConsToPrim of both fluids (the gas march has
-// left its conserved state in P.gas.cons0) and, with g.dt_dev, both fluids' timestep limits
-void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g, int fluid, int recon, int riemann, hipStream_t s,
-                       bool finish = false);
-// kernels_ppm.hip: the PPM tile march (Cartesian 3-D, one gas species; ppm_march_covers in kernels_stage_cell.hip)
-bool ppm_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas);
+// fluid 1 with pl.finish_in_march: the dust march also runs DragSource + SetAuxillaryFields + ConsToPrim of both fluids (the
+// gas march has left its conserved state in P.gas.cons0) and, with g.dt_dev, both fluids' timestep limits
+void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int fluid, int riemann,
+                       hipStream_t s);
+// kernels_ppm.hip: the PPM tile march (Cartesian 3-D, one gas species)
 void launch_stage_ppm(const PackView &P, const artemis_stage_general_args_t &g, int riemann, hipStream_t s);
 // kernels_diffusion.hip
 void launch_zero_diffusion_flux(const PackView &P, hipStream_t s);
@@ -107,14 +104,8 @@ void launch_ml_face_fluxes(const PackView &P, const artemis_stage_general_args_t
                            int recon_dust, int riemann_dust, const artemis_ml_face_box_t *boxes, int nboxes, hipStream_t s);
 void launch_ml_stage_fixup(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
                            int recon_dust, int riemann_dust, const artemis_ml_fix_cell_t *cells, int ncells, hipStream_t s);
-int stage_general_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
-                          int recon_dust, int riemann_dust);
-int stage_general_dust_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
-                          int recon_dust, int riemann_dust);
-bool stage2d_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas, int recon_dust,
-                    int riemann_dust);
-void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas, int riemann_dust,
-                    hipStream_t s);
+void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int riemann_gas,
+                    int riemann_dust, hipStream_t s);
 // kernels_amr.hip
 void launch_ml_exchange(const PackView &P, const artemis_ml_pack_t &ml, const artemis_ml_op_t *ops, int nops, double *sbuf,
                         const double *rbuf, hipStream_t s);

@@ -975,64 +975,19 @@ void launch_sys(const PackView &P, const CurvK &k, int riemann, int recon, bool 
 }
 } // namespace
 
-// Gas (one species), PCM / PLM, with the pointwise tasks the kernel folds in; diffusion only as
-// artemis_hip_viscous_source's sums (the flux-array form stays on kernels_fused.hip's instantiation).  Dust species
-// beside it, drag and N-body gravity are fine: the dust runs on its own march (curv_march_covers_dust) or on its
-// cell-centred kernel, and the drag finish couples the fluids (launch_stage_cell).
-bool curv_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas) {
-  if (opt(OPT_NO_CURV_MARCH)) return false;
-  if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false;
-  if (P.gas.ns != 1 || P.dust.ns > ARTEMIS_MAX_DUST_SPECIES || P.ng < 2) return false;
-  // Cartesian packs with the pointwise sources the tuned kernel (kernels_fused.hip) and the 2-D row march do not carry --
-  // gravity, viscosity as sums, the shearing box (a Cartesian pack's rotating frame), dust species beside the gas -- on
-  // the same march: plain PLM, every metric factor 1 (SYS = cartesian instantiations)
-  if (P.coords == ARTEMIS_CARTESIAN && (g.nbody_n || P.ndim < 2 || opt(OPT_NO_CART_MARCH))) return false;
-  // NO_CART_DUST_MARCH: Cartesian packs with dust or the shearing box, and packs with several dust species on any
-  // system, keep the kernels they had before the march took them
-  if (opt(OPT_NO_CART_DUST_MARCH) &&
-      (P.dust.ns > 1 || (P.coords == ARTEMIS_CARTESIAN && (P.dust.ns != 0 || g.rf_omega != 0.0))))
-    return false;
-  if (g.strat_faces) return false; // (conditions inside the kernel: the row march only)
-  if (!g.pcm && recon_gas == ARTEMIS_PPM) return false;
-  if (g.cooling) return false;
-  if (g.diffusion && !g.diffusion_sums) return false;
-  if (g.nbody_n && P.coords != ARTEMIS_CYLINDRICAL && P.coords != ARTEMIS_SPHERICAL3D) return false;
-  if (g.gravity && g.gravity->type != ARTEMIS_GRAVITY_UNIFORM && g.gravity->type != ARTEMIS_GRAVITY_POINT &&
-      g.gravity->type != ARTEMIS_GRAVITY_BINARY)
-    return false;
-  // the systems by dimensionality (geometry.hpp:38-56 CoordSelect): anything else keeps the older kernel
-  const int nd = P.ndim;
-  switch (P.coords) {
-  case ARTEMIS_CARTESIAN: return nd >= 2;
-  case ARTEMIS_CYLINDRICAL: return nd >= 2;
-  case ARTEMIS_SPHERICAL1D: return nd == 1;
-  case ARTEMIS_SPHERICAL2D: return nd == 2;
-  case ARTEMIS_SPHERICAL3D: return nd == 3;
-  case ARTEMIS_AXISYMMETRIC: return nd >= 1;
-  default: return false;
-  }
-}
-
-// The dust species beside it on the same march (DUST instantiations, one launch for all species): PCM / PLM, HLLE / LLF
-bool curv_march_covers_dust(const PackView &P, const artemis_stage_general_args_t &g, int recon_dust, int riemann_dust) {
-  if (P.dust.ns < 1 || opt(OPT_NO_CURV_DUST_MARCH)) return false;
-  if (!g.pcm && recon_dust == ARTEMIS_PPM) return false;
-  return riemann_dust == ARTEMIS_HLLE || riemann_dust == ARTEMIS_LLF;
-}
-
 // fluid 0: the gas march; fluid 1: the dust march (same tiles, same chunks)
-void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g, int fluid, int recon_in, int riemann, hipStream_t s,
-                       bool finish) {
+void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int fluid, int riemann,
+                       hipStream_t s) {
   const bool dust = fluid != 0;
   CurvK k;
   k.gam0 = g.gam0, k.gam1 = g.gam1, k.beta_dt = g.beta_dt, k.bdt = g.bdt, k.cfl = dust ? g.cfl_dust : g.cfl_gas;
   k.bdt_ptr = g.beta_dt_dev;
   if (dust) k.prim_in = g.dust_in, k.prim_u1 = g.dust_u1, k.prim_out = g.dust_out;
   else k.prim_in = g.gas_in, k.prim_u1 = g.gas_u1, k.prim_out = g.gas_out;
-  k.to_cons = (g.drag || g.defer_finish == 1) ? 1 : 0;
+  k.to_cons = pl.to_cons ? 1 : 0;
   k.finish = 0, k.gas_out = g.gas_out, k.cfl_gas = g.cfl_gas;
   std::memset(&k.drag, 0, sizeof k.drag);
-  if (dust && finish) { // the dust march couples the fluids itself and writes both fluids' primitives (stage_finish_in_march)
+  if (dust && pl.finish_in_march) { // the dust march couples the fluids itself and writes both fluids' primitives (stage_finish_in_march)
     k.to_cons = 0, k.finish = 1;
     k.drag.stokes = (g.drag->model == ARTEMIS_DRAG_STOKES) ? 1 : 0, k.drag.tau = g.drag->tau[0], k.drag.scale = g.drag->scale;
     k.drag.grain_density = g.drag->grain_density, k.drag.size = g.drag->sizes[0];
@@ -1054,14 +1009,14 @@ void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g,
   k.nchunk = (P.ndim > 2) ? (nz + kch - 1) / kch : 1;
   k.kchunk = (nz + k.nchunk - 1) / k.nchunk;
   k.nchunk = (P.ndim > 2) ? (nz + k.kchunk - 1) / k.kchunk : 1;
-  k.grav_on = (g.gravity && (g.time >= g.gravity->tstart) && (g.time < g.gravity->tstop)) ? 1 : 0;
+  k.grav_on = pl.grav_on ? 1 : 0;
   if (k.grav_on) k.grav = *g.gravity;
   k.rfc_on = (g.rf_omega != 0.0) ? 1 : 0, k.rf_omega = g.rf_omega, k.rf_qshear = g.rf_qshear;
   k.diff_on = (!dust && g.diffusion != nullptr) ? 1 : 0;
   k.dsum = dust ? nullptr : g.diffusion_sums;
   // (dust: every species marches the same tiles and chunks in the same launch, the species as the grid's slowest index)
   const unsigned grid = static_cast<unsigned>(tiles * k.nchunk * (dust ? P.dust.ns : 1));
-  const int recon = g.pcm ? ARTEMIS_PCM : recon_in;
+  const int recon = dust ? pl.recon_dust : pl.recon_gas;
   const bool d3 = P.ndim > 2;
 #define CURV_SYS(SYSV, D3V)                                                          \
   do {                                                                               \
@@ -1069,7 +1024,7 @@ void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g,
     else launch_sys<SYSV, D3V>(P, k, riemann, recon, narrow, grid, s);               \
   } while (0)
   switch (P.coords) {
-  case ARTEMIS_CARTESIAN: // (2-D and 3-D: curv_march_covers)
+  case ARTEMIS_CARTESIAN: // (2-D and 3-D)
     if (d3) CURV_SYS(ARTEMIS_CARTESIAN, true);
     else CURV_SYS(ARTEMIS_CARTESIAN, false);
     break;

@@ -1175,7 +1175,7 @@ bool viscous_source_covers(const PackView &P) {
   if (opt(OPT_NO_VISC_SOURCE)) return false;
   if (P.ndim != 3 || P.gas.ns != 1 || P.ng < 2) return false;
   if (P.coords == ARTEMIS_SPHERICAL1D || P.coords == ARTEMIS_SPHERICAL2D) return false; // (never 3-D blocks)
-  if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false;
+  if (!offsets_fit(P)) return false;
   return (P.ie - P.is + 1) >= 8 && (P.je - P.js + 1) >= 8;
 }
 void launch_viscous_source(const PackView &P, const artemis_diffusion_t &D, double dt, const double *dt_dev, double *const *out,

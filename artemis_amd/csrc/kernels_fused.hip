@@ -1446,8 +1446,6 @@ int launch_stage_fused_redo_shell(const PackView &P, const artemis_stage_args_t 
   return 0;
 }
 
-// the tile march addresses cells with 32-bit byte offsets (fused_device.hpp gld / gst)
-static bool offsets_fit(const PackView &P) { return static_cast<long>(P.nk) * P.nj * P.ni < (1L << 29); }
 int launch_stage_fused(const PackView &P, const artemis_stage_args_t &a, int riemann, int recon,
                        hipStream_t s) {
   if (recon == ARTEMIS_PPM) return 3; // PPM stays on the per-task path
@@ -1574,7 +1572,7 @@ int launch_stage_fused(const PackView &P, const artemis_stage_args_t &a, int rie
 // per-task chain, so the task's outputs do not change.
 bool fused_flux_covers(const PackView &P, int recon) {
   if (opt(OPT_NO_TILED_FLUX)) return false;
-  if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false;
+  if (!offsets_fit(P)) return false;
   if (P.coords != ARTEMIS_CARTESIAN || P.gas.ns != 1 || P.ng < 2 || P.ndim < 2) return false;
   if (recon != ARTEMIS_PCM && recon != ARTEMIS_PLM) return false;
   return (P.ie - P.is + 1) >= FTX && (P.je - P.js + 1) >= FTY;
@@ -1625,19 +1623,6 @@ int launch_flux_fused(const PackView &P, int riemann, int recon, hipStream_t s) 
 }
 
 // ---- curvilinear decks through artemis_hip_stage_general -----------------------------------------
-// Gas (one species) on any non-Cartesian system, PCM / PLM, with the pointwise tasks plane_update_curv folds
-// in; everything else stays on the cell-centred kernels.
-bool fused_curv_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas) {
-  if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false;
-  if (P.coords == ARTEMIS_CARTESIAN || P.gas.ns != 1 || P.dust.ns != 0 || P.ng < 2) return false;
-  if (!g.pcm && recon_gas == ARTEMIS_PPM) return false;
-  if (g.drag || g.cooling || g.nbody_n || g.defer_finish) return false;
-  if (g.gravity && g.gravity->type != ARTEMIS_GRAVITY_UNIFORM && g.gravity->type != ARTEMIS_GRAVITY_POINT &&
-      g.gravity->type != ARTEMIS_GRAVITY_BINARY)
-    return false;
-  return true;
-}
-
 namespace {
 template <int RIEMANN, int RECON>
 void launch_curv(const PackView &P, const StageK &k, const SrcArg<true> &src, bool has_u1, bool dt, hipStream_t s) {
@@ -1654,7 +1639,7 @@ void launch_curv(const PackView &P, const StageK &k, const SrcArg<true> &src, bo
 }
 } // namespace
 
-void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
+void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int riemann_gas,
                              hipStream_t s) {
   StageK k;
   k.gam0 = g.gam0, k.gam1 = g.gam1, k.beta_dt = g.beta_dt, k.bdt = g.bdt, k.cfl = g.cfl_gas;
@@ -1676,7 +1661,7 @@ void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args
   k.outflow = 0, k.outflow_blk = 0, k.outflow_pb = 0;
   k.xcd_swizzle = opt(OPT_FUSED_NO_SWIZZLE) ? 0 : 1;
   SrcArg<true> src;
-  src.v.grav_on = (g.gravity && (g.time >= g.gravity->tstart) && (g.time < g.gravity->tstop)) ? 1 : 0;
+  src.v.grav_on = pl.grav_on ? 1 : 0;
   if (src.v.grav_on) src.v.grav = *g.gravity;
   src.v.rfc_on = (g.rf_omega != 0.0) ? 1 : 0, src.v.rf_omega = g.rf_omega;
   src.v.diff_on = (g.diffusion != nullptr) ? 1 : 0;
@@ -1684,7 +1669,7 @@ void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args
   src.v.dsum = src.v.diff_on ? g.diffusion_sums : nullptr;
   const bool has_u1 = (g.gas_u1 != g.gas_in);
   const bool dt = (g.dt_dev != nullptr);
-  const int recon = g.pcm ? ARTEMIS_PCM : recon_gas;
+  const int recon = pl.recon_gas;
 #define RC(RS)                                                                             \
   case RS:                                                                                 \
     if (recon == ARTEMIS_PCM) launch_curv<RS, 0>(P, k, src, has_u1, dt, s);                \

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void stage_ppm_kernel(const PackView P, con
 }
 } // namespace
 
-// Gas of a pack ppm_march_covers admits (kernels_stage_cell.hip): the whole stage, timestep limit included
+// Gas of a pack the stage plan sends here: the whole stage, timestep limit included
 void launch_stage_ppm(const PackView &P, const artemis_stage_general_args_t &g, int riemann, hipStream_t s) {
   PpmK k;
   k.gam0 = g.gam0, k.gam1 = g.gam1, k.beta_dt = g.beta_dt, k.bdt = g.bdt, k.cfl = g.cfl_gas;

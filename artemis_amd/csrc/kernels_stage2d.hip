@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void stage2d_kernel(const PackView P, const
       e_r[n] = a.du1[b * 4 * ND + n], e_1[n] = a.du1[b * 4 * ND + ND + 3 * n + 0];
       e_2[n] = a.du1[b * 4 * ND + ND + 3 * n + 1], e_3[n] = a.du1[b * 4 * ND + ND + 3 * n + 2];
     }
-    // element offsets in 32 bits (fused_device.hpp gld / gst: SGPR base + one VGPR byte offset per cell); stage2d_covers
+    // element offsets in 32 bits (fused_device.hpp gld / gst: SGPR base + one VGPR byte offset per cell); the stage plan
     // refuses blocks of 2^29 zones or more
     const unsigned sj = static_cast<unsigned>(P.sj);
     const unsigned col = static_cast<unsigned>(il); // k = 0 in a 2-D block
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256, 1) void stage2d_kernel(const PackView P, const
             sieg = GD((ue_cons > fg.de_switch * e_cons) ? ue_cons : u0.eg, ru);
             sieg = amax(sieg, fg.siefloor);
           }
-          const double mu = 0.0; // damp_to_visc is not routed here (stage2d_covers refuses it)
+          const double mu = 0.0; // damp_to_visc is not routed here (the stage plan refuses it)
           const double vR = -1.5 * mu / (cv.R * dg);
           const double vt[3] = {cv.e1 * vR, cv.e2 * vR, cv.e3 * vR};
           double fdd[3] = {0., 0., 0.}, fvd[3] = {0., 0., 0.};
@@ -742,30 +742,13 @@ void launch_rc(const PackView &P, int recon, const S2Args &a, hipStream_t s) {
 
 } // namespace
 
-// Does the 2-D row-march stage cover this call of artemis_hip_stage_general?
-bool stage2d_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas, int recon_dust,
-                    int riemann_dust) {
-  if (P.coords != ARTEMIS_CARTESIAN || P.ndim != 2 || P.ng < 2) return false;
-  if (static_cast<long>(P.nj) * P.ni >= (1L << 29)) return false; // 32-bit cell offsets
-  if (P.gas.ns != 1 || P.dust.ns > 2) return false;
-  if (recon_gas == ARTEMIS_PPM || (P.dust.ns && (recon_dust != recon_gas || riemann_dust == ARTEMIS_HLLC))) return false;
-  if (g.diffusion || g.cooling || g.nbody_n || g.defer_finish) return false;
-  if (g.strat_faces && (g.strat_faces != 15 || P.nb != 1 || P.ie - P.is < 1)) return false; // (all four faces of ONE block)
-  if (g.drag && (g.drag->type != ARTEMIS_DRAG_SIMPLE_DUST || g.drag->damp_visc || P.dust.ns == 0)) return false;
-  if (g.gravity && g.gravity->type != ARTEMIS_GRAVITY_UNIFORM && g.gravity->type != ARTEMIS_GRAVITY_POINT &&
-      g.gravity->type != ARTEMIS_GRAVITY_BINARY)
-    return false;
-  (void)riemann_gas;
-  return true;
-}
-
-void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas, int riemann_dust,
-                    hipStream_t s) {
+void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int riemann_gas,
+                    int riemann_dust, hipStream_t s) {
   S2Args a;
   a.gam0 = g.gam0, a.gam1 = g.gam1, a.beta_dt = g.beta_dt, a.bdt = g.bdt, a.bdt_ptr = g.beta_dt_dev;
   a.gin = g.gas_in, a.gu1 = g.gas_u1, a.gout = g.gas_out, a.din = g.dust_in, a.du1 = g.dust_u1, a.dout = g.dust_out;
   a.has_u1 = (g.gas_u1 != g.gas_in) ? 1 : 0;
-  a.grav_on = (g.gravity && (g.time >= g.gravity->tstart) && (g.time < g.gravity->tstop)) ? 1 : 0;
+  a.grav_on = pl.grav_on ? 1 : 0;
   if (a.grav_on) a.grav = *g.gravity;
   a.rf_on = (g.rf_omega != 0.0) ? 1 : 0, a.rf_omega = g.rf_omega, a.rf_qshear = g.rf_qshear;
   a.drag_on = g.drag ? 1 : 0;
@@ -806,7 +789,7 @@ void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, in
     a.redo_cnt = g_redo2d.cnt, a.redo_done = g_redo2d.cnt + 1, a.redo_list = g_redo2d.list;
     a.redo_cap = static_cast<unsigned>(std::min<size_t>(g_redo2d.cap, 0xffffffffu));
   }
-  const int recon = g.pcm ? ARTEMIS_PCM : recon_gas;
+  const int recon = pl.recon_gas;
   const int rd = (P.dust.ns && riemann_dust == ARTEMIS_LLF) ? 2 : 1;
 #define RR(G_)                                             \
   case G_:                                                 \

@@ -492,7 +492,7 @@ CellStageArgs cell_args(const PackView &P, const artemis_stage_general_args_t &g
   a.bdt_ptr = g.beta_dt_dev;
   a.in = a.u1 = a.out = nullptr;
   a.to_cons = 0;
-  a.grav_on = (g.gravity && (g.time >= g.gravity->tstart) && (g.time < g.gravity->tstop)) ? 1 : 0;
+  a.grav_on = gravity_active(g) ? 1 : 0;
   if (a.grav_on) a.grav = *g.gravity;
   const bool cart = (P.coords == ARTEMIS_CARTESIAN);
   a.rf_on = (g.rf_omega != 0.0) && cart, a.rf_omega = g.rf_omega, a.rf_qshear = g.rf_qshear;
@@ -589,13 +589,13 @@ void launch_ml_face_fluxes(const PackView &P, const artemis_stage_general_args_t
                            int recon_dust, int riemann_dust, const artemis_ml_face_box_t *boxes, int nboxes, hipStream_t s) {
   if (nboxes <= 0) return;
   if (P.gas.ns) {
-    const int recon = g.pcm ? ARTEMIS_PCM : recon_gas;
+    const int recon = effective_recon(g, recon_gas);
     if (riemann_gas == ARTEMIS_HLLC) launch_faces_recon<0, 0>(P, recon, g.gas_in, boxes, nboxes, s);
     else if (riemann_gas == ARTEMIS_HLLE) launch_faces_recon<0, 1>(P, recon, g.gas_in, boxes, nboxes, s);
     else launch_faces_recon<0, 2>(P, recon, g.gas_in, boxes, nboxes, s);
   }
   if (P.dust.ns) {
-    const int recon = g.pcm ? ARTEMIS_PCM : recon_dust;
+    const int recon = effective_recon(g, recon_dust);
     if (riemann_dust == ARTEMIS_HLLE) launch_faces_recon<1, 1>(P, recon, g.dust_in, boxes, nboxes, s);
     else launch_faces_recon<1, 2>(P, recon, g.dust_in, boxes, nboxes, s);
   }
@@ -610,14 +610,14 @@ void launch_ml_stage_fixup(const PackView &P, const artemis_stage_general_args_t
   a.to_cons = g.defer_finish ? 1 : 0;
   if (P.gas.ns) {
     a.in = g.gas_in, a.u1 = g.gas_u1, a.out = g.gas_out;
-    const int recon = g.pcm ? ARTEMIS_PCM : recon_gas;
+    const int recon = effective_recon(g, recon_gas);
     if (riemann_gas == ARTEMIS_HLLC) launch_fix_recon<0, 0>(P, recon, a, s);
     else if (riemann_gas == ARTEMIS_HLLE) launch_fix_recon<0, 1>(P, recon, a, s);
     else launch_fix_recon<0, 2>(P, recon, a, s);
   }
   if (P.dust.ns) {
     a.in = g.dust_in, a.u1 = g.dust_u1, a.out = g.dust_out;
-    const int recon = g.pcm ? ARTEMIS_PCM : recon_dust;
+    const int recon = effective_recon(g, recon_dust);
     if (riemann_dust == ARTEMIS_HLLE) launch_fix_recon<1, 1>(P, recon, a, s);
     else launch_fix_recon<1, 2>(P, recon, a, s);
   }
@@ -641,104 +641,48 @@ void launch_stage_epilogue(const PackView &P, const artemis_stage_general_args_t
   }
 }
 
-// What the PPM tile march (kernels_ppm.hip, variant 4) takes: one gas species alone on Cartesian 3-D blocks, PPM4 with
-// its three ghost zones, every ghost zone filled by the caller, none of the optional tasks.  Everything else -- PPM
-// packs with dust, the PCM predictor stage of vl2, 1-D / 2-D, curvilinear systems, refined meshes (defer_finish != 0)
-// -- keeps the variant it had.
-bool ppm_march_covers(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas) {
-  if (P.coords != ARTEMIS_CARTESIAN || P.ndim != 3) return false;
-  if (P.gas.ns != 1 || P.dust.ns != 0) return false;
-  if (g.pcm || recon_gas != ARTEMIS_PPM || P.ng < 3) return false;
-  if (static_cast<long>(P.nk) * P.nj * P.ni >= (1L << 29)) return false; // (32-bit element offsets)
-  if (g.gravity || g.rf_omega != 0.0 || g.drag || g.diffusion || g.cooling || g.nbody_n) return false;
-  return g.defer_finish == 0 && g.strat_faces == 0;
-}
-
-int stage_general_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
-                          int recon_dust, int riemann_dust) {
-  if (!opt(OPT_NO_PPM_MARCH) && ppm_march_covers(P, g, recon_gas)) return 4;
-  if (!opt(OPT_NO_STAGE2D) && stage2d_covers(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust)) return 1;
-  if (!opt(OPT_NO_FUSED_CURV)) {
-    if (curv_march_covers(P, g, recon_gas)) return 3;
-    if (fused_curv_covers(P, g, recon_gas)) return 2;
-  }
-  return 0;
-}
-
-// One dust species coupled by simple_dust drag: the dust march does the coupled update, SetAuxillaryFields and
-// ConsToPrim of both fluids on its registers (no conserved round trip of the dust, no finish launch)
-static bool dust_finish_in_march(const PackView &P, const artemis_stage_general_args_t &g) {
-  return g.drag && g.defer_finish != 1 && !opt(OPT_NO_DRAG_IN_MARCH) && drag_finish_in_march(P, *g.drag);
-}
-
-// Which kernel the DUST of this call runs on: -1 no dust; 0 cell-centred; 1 row march; 3 dust march; 5 dust march with
-// the drag finish inside it
-int stage_general_dust_variant(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas, int riemann_gas,
-                               int recon_dust, int riemann_dust) {
-  if (P.dust.ns == 0) return -1;
-  const int variant = stage_general_variant(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust);
-  if (variant == 1) return 1;
-  if (variant != 3 || !curv_march_covers_dust(P, g, recon_dust, riemann_dust)) return 0;
-  return dust_finish_in_march(P, g) ? 5 : 3;
-}
-
+// One call of artemis_hip_stage_general: the kernels the stage plan names (stage_plan.hip), then the launches it lists
 void launch_stage_cell(const PackView &P, const artemis_stage_general_args_t &g, int recon_gas,
                        int riemann_gas, int recon_dust, int riemann_dust, hipStream_t s) {
-  // 2-D Cartesian gas (+ <= 2 dust species) with the pointwise sources: the row-march kernel does the whole
-  // stage of both fluids, drag, aux, c2p and dt in one pass (kernels_stage2d.hip; same bits)
-  const int variant = stage_general_variant(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust);
-  if (variant == 1) {
-    launch_stage2d(P, g, recon_gas, riemann_gas, riemann_dust, s);
-    return;
-  }
-  if (variant == 4) { // Cartesian 3-D gas with PPM: the whole stage and its timestep limit on the tile march (kernels_ppm.hip)
-    launch_stage_ppm(P, g, riemann_gas, s);
-    return;
-  }
-  if (variant == 2) { // curvilinear gas with diffusion from stored flux arrays: the older march, geometry in registers
-    launch_stage_fused_curv(P, g, recon_gas, riemann_gas, s);
-    return;
-  }
-  // defer_finish: 1 = stop at the conserved state (the caller finishes every zone); 2 = finish every zone here, the caller
-  // re-finishes its listed fix-up zones (artemis_hip_stage_finish_cells); 0 = no fix-up follows
-  const bool defer = g.defer_finish == 1;
-  const bool to_cons = g.drag || defer;
+  const StagePlan pl = plan_stage_general(P, g, recon_gas, riemann_gas, recon_dust, riemann_dust);
   CellStageArgs a = cell_args(P, g);
-  a.to_cons = to_cons ? 1 : 0;
-  if (variant == 3) { // the streaming tile march with its geometry in LDS tables (kernels_curv.hip)
-    launch_stage_curv(P, g, 0, recon_gas, riemann_gas, s);
-  } else if (P.gas.ns) {
+  a.to_cons = pl.to_cons ? 1 : 0;
+  switch (pl.gas) {
+  // the row march: both fluids, drag, aux, c2p and dt in one pass; the PPM and the older march (geometry in registers): the
+  // whole gas stage and its timestep limit; the streaming tile march with its geometry in LDS tables: one fluid per launch
+  case GasKernel::RowMarch: launch_stage2d(P, g, pl, riemann_gas, riemann_dust, s); break;
+  case GasKernel::PpmMarch: launch_stage_ppm(P, g, riemann_gas, s); break;
+  case GasKernel::FusedCurv: launch_stage_fused_curv(P, g, pl, riemann_gas, s); break;
+  case GasKernel::TileMarch: launch_stage_curv(P, g, pl, 0, riemann_gas, s); break;
+  case GasKernel::Cell:
+    if (!P.gas.ns) break;
     a.in = g.gas_in, a.u1 = g.gas_u1, a.out = g.gas_out;
-    const int recon = g.pcm ? ARTEMIS_PCM : recon_gas;
-    if (riemann_gas == ARTEMIS_HLLC) launch_recon<0, 0>(P, recon, a, s);
-    else if (riemann_gas == ARTEMIS_HLLE) launch_recon<0, 1>(P, recon, a, s);
-    else launch_recon<0, 2>(P, recon, a, s);
+    if (riemann_gas == ARTEMIS_HLLC) launch_recon<0, 0>(P, pl.recon_gas, a, s);
+    else if (riemann_gas == ARTEMIS_HLLE) launch_recon<0, 1>(P, pl.recon_gas, a, s);
+    else launch_recon<0, 2>(P, pl.recon_gas, a, s);
+    break;
   }
-  const bool dust_march = variant == 3 && curv_march_covers_dust(P, g, recon_dust, riemann_dust);
-  const bool finish_in_march = dust_march && dust_finish_in_march(P, g);
-  if (dust_march) { // every dust species on the same march, one launch (kernels_curv.hip, DUST instantiations)
-    launch_stage_curv(P, g, 1, recon_dust, riemann_dust, s, finish_in_march);
-  } else if (P.dust.ns) {
+  switch (pl.dust) {
+  case DustKernel::None:
+  case DustKernel::RowMarch: break; // (inside the gas launch)
+  case DustKernel::TileMarch: launch_stage_curv(P, g, pl, 1, riemann_dust, s); break; // (every species in one launch)
+  case DustKernel::Cell:
     a.in = g.dust_in, a.u1 = g.dust_u1, a.out = g.dust_out;
-    const int recon = g.pcm ? ARTEMIS_PCM : recon_dust;
-    if (riemann_dust == ARTEMIS_HLLE) launch_recon<1, 1>(P, recon, a, s);
-    else launch_recon<1, 2>(P, recon, a, s);
+    if (riemann_dust == ARTEMIS_HLLE) launch_recon<1, 1>(P, pl.recon_dust, a, s);
+    else launch_recon<1, 2>(P, pl.recon_dust, a, s);
+    break;
   }
-  if (defer) return; // the caller finishes (artemis_hip_stage_finish) once its fix-up has run
-  if (finish_in_march) return; // (both fluids' primitives and timestep limits are done)
   PackView Q = P; // the new state: prim tables are the out tables
   Q.gas.prim = g.gas_out, Q.dust.prim = g.dust_out;
-  if (g.drag) { // coupled update on cons0, then SetAuxillaryFields and ConsToPrim into the out tables
-    if (!launch_drag_finish(Q, *g.drag, g.bdt, g.beta_dt_dev, s)) { // one pass when one gas species is coupled
-      launch_drag_source(Q, *g.drag, g.bdt, g.beta_dt_dev, s);
-      if (Q.gas.ns) launch_set_aux(Q, s);
-      launch_cons_to_prim(Q, s);
-    }
+  // coupled update on cons0, then SetAuxillaryFields and ConsToPrim into the out tables
+  if (pl.drag_finish && !launch_drag_finish(Q, *g.drag, g.bdt, g.beta_dt_dev, s)) { // one pass when one gas species is coupled
+    launch_drag_source(Q, *g.drag, g.bdt, g.beta_dt_dev, s);
+    if (Q.gas.ns) launch_set_aux(Q, s);
+    launch_cons_to_prim(Q, s);
   }
-  if (g.dt_dev) { // EstimateTimestepMesh of the new state (gas.cpp:411-433, dust.cpp:256-272)
-    if (Q.gas.ns && !(variant == 3 && !to_cons)) launch_estimate_dt(Q, ARTEMIS_GAS, g.cfl_gas, g.dt_dev, s); // (the march has its own)
-    if (Q.dust.ns && !(dust_march && !to_cons)) launch_estimate_dt(Q, ARTEMIS_DUST, g.cfl_dust, g.dt_dev, s);
-  }
+  // EstimateTimestepMesh of the new state (gas.cpp:411-433, dust.cpp:256-272)
+  if (pl.dt_gas) launch_estimate_dt(Q, ARTEMIS_GAS, g.cfl_gas, g.dt_dev, s);
+  if (pl.dt_dust) launch_estimate_dt(Q, ARTEMIS_DUST, g.cfl_dust, g.dt_dev, s);
 }
 
 } // namespace artemis
