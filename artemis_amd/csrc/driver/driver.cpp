@@ -30,6 +30,7 @@
 #include "../geometry_core.hpp"
 #include "parameter_input.hpp"
 #include "block_tree.hpp"
+#include "checkpoint_hooks.hpp"
 
 #define SQR(x) ((x) * (x))
 typedef double Real;
@@ -3721,6 +3722,122 @@ static bool remesh(artemis_sim &h, bool initial, long force_refine_gid = -1, con
   }
   return true;
 }
+
+// =======================================================================================
+// What checkpoint.cpp reaches of the state (checkpoint_hooks.hpp)
+namespace artemis_ckpt {
+
+void set_error(const std::string &msg) { g_sim_err = msg; }
+std::string dead_reason(const artemis_sim_t *sim) { return sim->dead; }
+const artemis_comm_t *comm_of(const artemis_sim_t *sim) { return sim->has_comm ? &sim->comm : nullptr; }
+
+void describe(const artemis_sim_t *sim, Meta &m) {
+  const artemis_sim_impl &S = *sim->p;
+  m.deck = sim->deck, m.overrides = sim->overrides, m.integrator = S.integrator;
+  m.time = S.time, m.dt = S.dt, m.ncycle = S.ncycle, m.remeshes = sim->remeshes, m.nblocks_global = S.nblocks_global;
+  m.rank = S.rank, m.nranks = S.nranks;
+  for (int d = 0; d < 3; ++d) m.mbnx[d] = S.mbnx[d];
+  m.ni = S.ni, m.nj = S.nj, m.nk = S.nk, m.nghost = S.ng, m.ndim = S.ndim;
+  m.ns_gas = S.gprim[S.base].nvar / 6, m.ns_dust = S.dprim[S.base].nvar / 4, m.coords = S.coords;
+  m.multilevel = S.multilevel ? 1 : 0, m.adaptive = (S.adaptive && S.refine_field) ? 1 : 0;
+  m.npart = static_cast<int>(S.particles.size());
+  m.nbuf = 1, m.base = 0;
+  for (int d = 0; d < S.ndim; ++d)
+    if (S.mbnx[d] < S.ng) m.nbuf = 3, m.base = S.base;
+  m.deref_count.clear();
+  for (const auto &kv : sim->deref_count)
+    m.deref_count.push_back({std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first), kv.second});
+  m.blocks.clear();
+  for (int b = 0; b < S.nb; ++b) m.blocks.push_back({S.blocks[b].level, S.blocks[b].lx[0], S.blocks[b].lx[1], S.blocks[b].lx[2]});
+}
+
+void prepare_save(artemis_sim_t *sim, std::vector<double> &nbody_rows) {
+  artemis_sim_impl &S = *sim->p;
+  S.fill_stale_ghosts();
+  CK(artemis_rt_device_sync(), "sync");
+  const size_t n = 7 * S.particles.size();
+  nbody_rows.assign(2 * n, 0.0);
+  for (size_t q = 0; q < n && q < S.particle_force.size(); ++q) nbody_rows[q] = S.particle_force[q];
+  if (n && S.nb_force_dev.p) {
+    CK(artemis_rt_memcpy_d2h(nbody_rows.data() + n, S.nb_force_dev.p, n * sizeof(double), S.stream), "d2h");
+    CK(artemis_rt_stream_sync(S.stream), "sync");
+  }
+}
+
+void download_block(artemis_sim_t *sim, int b, int which, double *gas, double *dust) {
+  artemis_sim_impl &S = *sim->p;
+  if (b < 0 || b >= S.nb || which < 0 || which > 2) throw std::runtime_error("checkpoint: bad block");
+  const int q = (S.base + which) % 3;
+  const Field &G = S.gprim[q], &D = S.dprim[q];
+  const size_t ng = static_cast<size_t>(S.gprim[S.base].nvar) * S.N, nd = static_cast<size_t>(S.dprim[S.base].nvar) * S.N;
+  if (G.ok()) CK(artemis_rt_memcpy_d2h(gas, G.var(b, 0), ng * sizeof(Real), S.stream), "d2h");
+  else std::fill(gas, gas + ng, 0.0);
+  if (D.ok()) CK(artemis_rt_memcpy_d2h(dust, D.var(b, 0), nd * sizeof(Real), S.stream), "d2h");
+  else std::fill(dust, dust + nd, 0.0);
+  CK(artemis_rt_stream_sync(S.stream), "sync");
+}
+
+artemis_sim_t *create_on_leaves(const std::string &deck, const std::vector<std::string> &overrides,
+                                const artemis_comm_t *comm, const std::vector<BlockKey> *leaves) {
+  std::unique_ptr<artemis_sim, void (*)(artemis_sim *)> s(new artemis_sim(), [](artemis_sim *p) { artemis_sim_destroy(p); });
+  s->deck = deck, s->overrides = overrides;
+  if (comm) s->comm = *comm, s->has_comm = true;
+  std::vector<artemis_host::Leaf> lv;
+  if (leaves)
+    for (const BlockKey &k : *leaves) {
+      artemis_host::Leaf l;
+      l.level = k[0], l.lx = {k[1], k[2], k[3]};
+      lv.push_back(l);
+    }
+  s->p = build_state(*s, leaves ? &lv : nullptr);
+  if (s->p->adaptive && s->p->refine_field && !artemis::opt(artemis::OPT_NO_POOL)) { // (as artemis_sim_create)
+    const long gb = artemis::opt(artemis::OPT_POOL_GB);
+    artemis_rt_pool_limit(static_cast<size_t>(gb > 0 ? gb : 64) << 30);
+  }
+  return s.release();
+}
+
+void upload_block(artemis_sim_t *sim, int b, int base, int which, const double *gas, const double *dust) {
+  artemis_sim_impl &S = *sim->p;
+  if (b < 0 || b >= S.nb || base < 0 || base > 2 || which < 0 || which > 2) throw std::runtime_error("checkpoint: bad block");
+  const int q = (base + which) % 3;
+  if (!S.gprim[q].ok()) S.gprim[q].alloc(S.nb, S.gprim[0].nvar, S.N);
+  if (!S.dprim[q].ok()) S.dprim[q].alloc(S.nb, S.dprim[0].nvar, S.N);
+  const Field &G = S.gprim[q], &D = S.dprim[q];
+  if (G.ok()) CK(artemis_rt_memcpy_h2d(G.var(b, 0), gas, static_cast<size_t>(G.nvar) * S.N * sizeof(Real), S.stream), "h2d");
+  if (D.ok()) CK(artemis_rt_memcpy_h2d(D.var(b, 0), dust, static_cast<size_t>(D.nvar) * S.N * sizeof(Real), S.stream), "h2d");
+  CK(artemis_rt_stream_sync(S.stream), "sync"); // (the caller reuses the host buffer)
+}
+
+void finish_restore(artemis_sim_t *sim, const Meta &m, const std::vector<double> &nbody_rows) {
+  artemis_sim_impl &S = *sim->p;
+  S.base = (m.nbuf == 3) ? m.base : 0, S.cons_valid = false, S.tiny_valid = false, S.ghosts_stale = false;
+  S.time = m.time, S.dt = m.dt, S.ncycle = m.ncycle;
+  sim->remeshes = m.remeshes;
+  sim->deref_count.clear();
+  for (const auto &e : m.deref_count) sim->deref_count[std::make_tuple(e[0], e[1], e[2], e[3])] = e[4];
+  S.place_binary();
+  const size_t n = 7 * S.particles.size();
+  if (n) {
+    if (nbody_rows.size() != 2 * n) throw std::runtime_error("checkpoint: the n-body rows do not match the deck's particles");
+    S.particle_force.assign(nbody_rows.begin(), nbody_rows.begin() + n);
+    bool pending = false;
+    for (size_t q = n; q < 2 * n; ++q) pending = pending || nbody_rows[q] != 0.0;
+    if (pending && S.nbody_in_stage) { // sums the saved run had not added to its host rows yet: back where they were
+      if (!S.nb_dev.p) {
+        S.nb_dev.alloc((sizeof(artemis_nbody_particle_t) * S.particles.size() + sizeof(double) - 1) / sizeof(double));
+        S.nb_force_dev.alloc(n);
+      }
+      CK(artemis_rt_memcpy_h2d(S.nb_force_dev.p, nbody_rows.data() + n, n * sizeof(double), S.stream), "h2d");
+      CK(artemis_rt_stream_sync(S.stream), "sync");
+    } else if (pending) {
+      for (size_t q = 0; q < n; ++q) S.particle_force[q] += nbody_rows[n + q];
+    }
+  }
+  CK(artemis_rt_device_sync(), "sync");
+}
+
+} // namespace artemis_ckpt
 
 extern "C" {
 

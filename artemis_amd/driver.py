@@ -246,6 +246,12 @@ def _declare(L):
     L.artemis_sim_errors.argtypes = [vp, C.POINTER(d)]
     L.artemis_sim_kernel_ms.restype = d
     L.artemis_sim_kernel_ms.argtypes = [vp, C.POINTER(l)]
+    L.artemis_sim_save.argtypes = [vp, C.c_char_p]
+    L.artemis_sim_restore.restype = vp
+    L.artemis_sim_restore.argtypes = [C.c_char_p, i, C.POINTER(C.c_char_p), C.POINTER(Comm)]
+    L.artemis_sim_checkpoint_describe.argtypes = [C.c_char_p, C.c_char_p, l]
+    L.artemis_sim_checkpoint_seconds.argtypes = [C.POINTER(d)]
+    L.artemis_sim_checkpoint_seconds.restype = None
     L._sim_declared = True
 
 
@@ -263,10 +269,57 @@ class Simulation:
         self.h = self.L.artemis_sim_create(text.encode(), len(overrides), ov, cptr)
         if not self.h:
             raise RuntimeError("artemis_sim_create: " + self.L.artemis_sim_last_error().decode())
+        self._attach()
+
+    def _attach(self):
         self._refresh_dims()
         ng_, nd_ = C.c_int(0), C.c_int(0)
         self.L.artemis_sim_species(self.h, C.byref(ng_), C.byref(nd_))
         self.ns_gas, self.ns_dust = ng_.value, nd_.value
+
+    def save(self, path):
+        """Write a checkpoint directory at `path` (collective over the ranks of the run; replaces an existing one).
+        Call it between evolve() calls."""
+        if self.L.artemis_sim_save(self.h, os.fspath(path).encode()):
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+
+    @classmethod
+    def restore(cls, path, overrides=(), comm=None, lib=None):
+        """The run a checkpoint holds, on this process' ranks (any count): continues bit for bit like the saved one.
+        overrides are applied after the stored ones ('parthenon/time/nlim=10'); runtime settings (set_path,
+        set_overlap, set_dropin) are not part of a checkpoint."""
+        self = cls.__new__(cls)
+        self.L = lib if lib is not None else capi.load()
+        _declare(self.L)
+        ov = (C.c_char_p * max(len(overrides), 1))(*[o.encode() for o in overrides])
+        self.comm = comm
+        cptr = C.byref(comm.struct) if comm is not None else None
+        self.h = self.L.artemis_sim_restore(os.fspath(path).encode(), len(overrides), ov, cptr)
+        if not self.h:
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+        self._attach()
+        return self
+
+    def checkpoint_seconds(self):
+        """The last save() or restore() of this thread: (total, device copies, checksums, file writes or reads) in seconds"""
+        out = (C.c_double * 4)()
+        self.L.artemis_sim_checkpoint_seconds(out)
+        return tuple(out)
+
+    @staticmethod
+    def describe_checkpoint(path, lib=None):
+        """Header fields of a checkpoint as a dict (no device, no communicator)."""
+        import json
+        L = lib if lib is not None else capi.load()
+        _declare(L)
+        p = os.fspath(path).encode()
+        n = L.artemis_sim_checkpoint_describe(p, None, 0)
+        if n < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        buf = C.create_string_buffer(n + 1)
+        if L.artemis_sim_checkpoint_describe(p, buf, n + 1) != n:
+            raise RuntimeError("the checkpoint changed while it was read")
+        return json.loads(buf.value.decode())
 
     def _refresh_dims(self):
         """Block layout of this rank (an adaptive mesh changes it between cycles)."""

@@ -164,6 +164,31 @@ int artemis_sim_history(artemis_sim_t *sim, double *out);
  * number of values, 0 if the pgen defines none. */
 int artemis_sim_errors(artemis_sim_t *sim, double *out);
 
+/* ---- checkpoint and restart ----------------------------------------------------------------------------------------
+ * A checkpoint is a directory with one plain binary part file per writing rank (part-00000.bin, ...; layout in
+ * artemis_amd/csrc/driver/checkpoint.cpp): the deck and overrides of the run, its clock (time, dt, ncycle), the block tree
+ * and the remesh history of an adaptive mesh, the n-body force sums, and per block the whole primitive arrays, ghost zones
+ * included, bytes as they are.  Everything else is rebuilt from the deck.  A restored run continues bit for bit like the
+ * run that was saved, on any number of ranks (n-body sums regroup across rank counts: equal to round-off there).
+ * Callers checkpoint between artemis_sim_evolve calls; the <parthenon/output*> blocks of a deck are not acted on.
+ *
+ * save: collective over the ranks of the simulation, which must see one file system.  Writes <path>.tmp and renames it
+ * once every rank has succeeded (an existing checkpoint at <path> is replaced).  Returns 0, non-zero on error. */
+int artemis_sim_save(artemis_sim_t *sim, const char *path);
+/* restore: collective over `comm` (NULL: one process); any rank count may read any checkpoint.  `overrides` are applied
+ * after the stored ones (nlim, tlim, cfl, solver, ...); one that changes block shape, nghost, species counts, coordinates
+ * or dimensionality is refused by name.  Runtime settings (artemis_sim_set_path / _set_overlap / _set_dropin) are not
+ * state: re-apply them.  A wrong magic or version, a truncated or missing part, a checksum mismatch or a directory entry
+ * that points outside its file return NULL (artemis_sim_last_error()). */
+artemis_sim_t *artemis_sim_restore(const char *path, int noverrides, const char *const *overrides,
+                                   const artemis_comm_t *comm);
+/* The header fields of a checkpoint as one JSON object; touches no device and needs no communicator.  Returns the length
+ * of the text (written with its NUL only if capacity exceeds it: call with NULL / 0 for the size), < 0 on error. */
+int artemis_sim_checkpoint_describe(const char *path, char *json_out, long capacity);
+/* Wall-clock seconds of the calling thread's last save or restore: out4 = {total (a restore: building the state from the
+ * deck included), device copies, checksums, file writes or reads}. */
+void artemis_sim_checkpoint_seconds(double *out4);
+
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured
  * with HIP events on the compute stream. */
