@@ -3782,5 +3782,61 @@ void oracle_riemann(int fluid, int solver, double gm1, const double *wl, const d
   out[0] = o.fd, out[1] = o.fmx, out[2] = o.fmy, out[3] = o.fmz, out[4] = o.fe, out[5] = o.feg;
   out[6] = o.pf, out[7] = o.vf;
 }
+// The same leaves over tables of n inputs (tests/test_reference_leaves.py holds them against the reference's
+// own headers, oracle/ref/ref_leaves.cpp); rows of wl / wr / out as in oracle_riemann.
+void oracle_plm_n(long n, const double *qm, const double *q, const double *qp, double *ql_ip1, double *qr_i) {
+  for (long t = 0; t < n; ++t) PLM(qm[t], q[t], qp[t], ql_ip1[t], qr_i[t]);
+}
+void oracle_ppm4_n(long n, const double *qmm, const double *qm, const double *q, const double *qp,
+                   const double *qpp, double *ql_ip1, double *qr_i) {
+  for (long t = 0; t < n; ++t) PPM4(qmm[t], qm[t], q[t], qp[t], qpp[t], ql_ip1[t], qr_i[t]);
+}
+void oracle_plm_g(long n, const double *qm, const double *q, const double *qp, const double *xm,
+                  const double *xc, const double *xp, const double *xf0, const double *xf1, const double *dx,
+                  double *ql_ip1, double *qr_i) {
+  for (long t = 0; t < n; ++t) {
+    const Real xf[2] = {xf0[t], xf1[t]};
+    PLM_G(qm[t], q[t], qp[t], ql_ip1[t], qr_i[t], xm[t], xc[t], xp[t], xf, dx[t]);
+  }
+}
+void oracle_riemann_n(int fluid, int solver, double gm1, long n, const double *wl, const double *wr,
+                      double *out) {
+  const int nv = (fluid == FL_GAS) ? 6 : 4;
+  for (long t = 0; t < n; ++t) oracle_riemann(fluid, solver, gm1, wl + t * nv, wr + t * nv, out + t * 8);
+}
+// {x1 of face 0, dx1, x2 of face 0, dx2, x3 of face 0, dx3}: the block's logical coordinates, Xf(d, i) = f0 + i * dx
+void oracle_geom(void *h, double *out) {
+  Sim &s = *static_cast<Sim *>(h);
+  for (int d = 0; d < 3; ++d) out[2 * d] = s.f0[d], out[2 * d + 1] = s.dx[d];
+}
+// What the hot path reads of Coords at n cells, 31 doubles a cell, in ref_coords' order: Volume, lower AreaX1..3,
+// x1v..x3v, hx1v..hx3v, dh{1,2,3}dx1, dh{1,2,3}dx2, dh{1,2,3}dx3, cell widths X1..X3, hx1..3 at the lower X1, X2
+// and X3 face centres.
+void oracle_coords(void *h, const int *k, const int *j, const int *i, long n, double *out) {
+  Sim &s = *static_cast<Sim *>(h);
+  for (long t = 0; t < n; ++t) {
+    double *o = out + t * 31;
+    const Coords c(s, k[t], j[t], i[t]);
+    Real a[2], w[3], hv[3], c1[3], c2[3];
+    o[0] = c.Volume();
+    c.GetFaceAreaX1(a), o[1] = a[0];
+    c.GetFaceAreaX2(a), o[2] = a[0];
+    c.GetFaceAreaX3(a), o[3] = a[0];
+    o[4] = c.x1v(), o[5] = c.x2v(), o[6] = c.x3v();
+    c.GetScaleFactors(hv), o[7] = hv[0], o[8] = hv[1], o[9] = hv[2];
+    c.GetConnX1(c1), c.GetConnX2(c2);
+    o[10] = c1[0], o[11] = c1[1], o[12] = c1[2];
+    o[13] = c2[0], o[14] = c2[1], o[15] = c2[2];
+    o[16] = 0.0, o[17] = 0.0, o[18] = 0.0; // x3dep() is false for every system (geometry.hpp:110-113)
+    c.GetCellWidths(w), o[19] = w[0], o[20] = w[1], o[21] = w[2];
+    Real xf[3][3];
+    c.FaceCenX1(0, xf[0]), c.FaceCenX2(0, xf[1]), c.FaceCenX3(0, xf[2]);
+    for (int d = 0; d < 3; ++d) {
+      o[22 + 3 * d + 0] = c.hx1(xf[d][0], xf[d][1], xf[d][2]);
+      o[22 + 3 * d + 1] = c.hx2(xf[d][0], xf[d][1], xf[d][2]);
+      o[22 + 3 * d + 2] = c.hx3(xf[d][0], xf[d][1], xf[d][2]);
+    }
+  }
+}
 
 } // extern "C"
