@@ -209,6 +209,8 @@ def load():
         "artemis_hip_deep_copy_conserved": (i, [PPk, vp]),
         "artemis_hip_estimate_dt": (i, [PPk, i, d, C.POINTER(d), vp]),
         "artemis_hip_estimate_dt_async": (i, [PPk, i, d, vp, vp]),
+        "artemis_hip_history_scratch_bytes": (C.c_size_t, [PPk]),
+        "artemis_hip_history_sums": (i, [PPk, vp, vp, vp]),
         "artemis_hip_apply_bc": (i, [PPk, C.POINTER(i), C.POINTER(BcParams), vp]),
         "artemis_hip_external_gravity": (i, [PPk, C.POINTER(Gravity), d, d, vp]),
         "artemis_hip_rotating_frame_force": (i, [PPk, d, d, d, d, vp]),
@@ -308,6 +310,7 @@ EXPORTS_HIP = [
     "artemis_hip_calculate_fluxes", "artemis_hip_apply_update", "artemis_hip_flux_source",
     "artemis_hip_set_aux", "artemis_hip_cons_to_prim", "artemis_hip_prim_to_cons", "artemis_hip_prim_to_cons_ghosts",
     "artemis_hip_deep_copy_conserved", "artemis_hip_estimate_dt", "artemis_hip_estimate_dt_async",
+    "artemis_hip_history_scratch_bytes", "artemis_hip_history_sums",
     "artemis_hip_apply_bc", "artemis_hip_stage_fused", "artemis_hip_stage_fused_redo_shell", "artemis_hip_metric_count",
     "artemis_hip_metric_fill", "artemis_hip_external_gravity", "artemis_hip_nbody_gravity", "artemis_hip_nbody_force_scratch",
     "artemis_hip_nbody_force_sums", "artemis_hip_timestep_all", "artemis_hip_redo_scratch_bytes", "artemis_hip_rotating_frame_force",

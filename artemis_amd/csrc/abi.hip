@@ -239,6 +239,20 @@ int artemis_hip_estimate_dt_async(const artemis_pack_t *p, int fluid, double cfl
   return after_launch("EstimateTimestepMesh");
 }
 
+size_t artemis_hip_history_scratch_bytes(const artemis_pack_t *p) {
+  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return 0;
+  const size_t nq = 6 * static_cast<size_t>(p->gas.nspecies) + 4 * static_cast<size_t>(p->dust.nspecies);
+  return static_cast<size_t>(artemis::history_workgroups(artemis::make_pack_view(*p))) * nq * sizeof(double);
+}
+int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_dev, double *scratch_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  if (!sums_dev || !scratch_dev) return fail(ARTEMIS_HIP_EINVAL, "history sums: null sums_dev or scratch_dev");
+  if ((p->gas.nspecies && !p->gas.prim) || (p->dust.nspecies && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "history sums: the primitive tables of every fluid in the pack are required");
+  artemis::launch_history_sums(artemis::make_pack_view(*p), sums_dev, scratch_dev, S(stream));
+  return after_launch("history_sums");
+}
+
 int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, double *dt_out,
                             void *stream) {
   if (!dt_out) return fail(ARTEMIS_HIP_EINVAL, "null dt_out");

@@ -31,6 +31,13 @@
 #include "parameter_input.hpp"
 #include "block_tree.hpp"
 #include "checkpoint_hooks.hpp"
+#include "outputs_hooks.hpp"
+
+// The device kernel of the history integrals is referenced weakly: a host that exports the driver's C ABI without it (the
+// CPU stand-in of the tests) sums on the host instead.
+extern "C" size_t artemis_hip_history_scratch_bytes(const artemis_pack_t *p) __attribute__((weak));
+extern "C" int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_dev, double *scratch_dev, void *stream)
+    __attribute__((weak));
 
 #define SQR(x) ((x) * (x))
 typedef double Real;
@@ -470,11 +477,15 @@ struct artemis_sim_impl {
   void step_fused(bool want_dt, bool device_dt);
   void step_ml_fused();
   void step_unfused();
-  long evolve(long max_cycles);
+  // owner: the handle whose output schedule the loop serves (NULL: none) -- see artemis_sim_evolve
+  long evolve(long max_cycles, artemis_sim_t *owner = nullptr);
+  void ensure_first_dt();
   void upload_block(Field &f, int b, const std::vector<Real> &h);
   std::vector<Real> download(const Field &f, int b);
   void lw_setup(bool eigen);
   int history(double *out);
+  DevBuf hist_sums, hist_scratch; // artemis_hip_history_sums: its result and its rows of partial sums, sized for this pack
+  int history_device(double *out);
   int errors(double *out);
 };
 
@@ -3247,15 +3258,32 @@ void artemis_sim_impl::step_unfused() {
 
 // parthenon EvolutionDriver::Execute + SetGlobalTimeStep (upstream, recalled; pinned by
 // tst/scripts/advection/advection.py:100-118).
-long artemis_sim_impl::evolve(long max_cycles) {
+void artemis_sim_impl::ensure_first_dt() {
+  if (ncycle == 0 && time == 0.0 && dt == DBL_MAX) {
+    Real v = new_dt_unfused();
+    if (has_comm && nranks > 1 && comm.allreduce_min(comm.ctx, &v)) throw std::runtime_error("allreduce failed");
+    dt = v;
+    if (tlim > 0.0 && time < tlim && (tlim - time) < dt) dt = tlim - time;
+  }
+}
+
+long artemis_sim_impl::evolve(long max_cycles, artemis_sim_t *owner) {
   auto global_min = [&](Real v) {
     if (has_comm && nranks > 1 && comm.allreduce_min(comm.ctx, &v)) throw std::runtime_error("allreduce failed");
     return v;
   };
-  if (ncycle == 0 && time == 0.0 && dt == DBL_MAX) {
-    dt = global_min(new_dt_unfused());
-    if (tlim > 0.0 && time < tlim && (tlim - time) < dt) dt = tlim - time;
-  }
+  ensure_first_dt();
+  // Output schedule of the handle (artemis_sim_enable_outputs): `deadline` is the earliest time at which a block becomes
+  // due.  It sizes the unsynchronised batches below exactly like tlim does and never touches dt; history rows are written
+  // from inside the loop, a due dump makes the loop return to the handle (`leave`), which saves between two calls.
+  const bool outs = owner && artemis_out::enabled(artemis_out::state_of(owner));
+  double deadline = outs ? artemis_out::deadline(artemis_out::state_of(owner)) : HUGE_VAL;
+  bool leave = false;
+  auto outputs_due = [&]() { // after the host's clock has moved
+    if (!outs || time < deadline) return;
+    leave = artemis_out::write_due(owner, true);
+    deadline = artemis_out::deadline(artemis_out::state_of(owner));
+  };
   for (auto &pr : kev) artemis_rt_event_destroy(pr.first), artemis_rt_event_destroy(pr.second);
   kev.clear();
   CK(artemis_rt_memset(signal.p, 0, 2 * sizeof(unsigned), stream), "memset"); // counter + sticky timeout flag
@@ -3316,27 +3344,32 @@ long artemis_sim_impl::evolve(long max_cycles) {
     if (!std::isfinite(dt) || !(dt > 0.0) || !std::isfinite(time))
       throw std::runtime_error("the device-side time loop produced a non-finite or non-positive dt");
   };
-  if (async_ok && tlim < 0.0) {
-    // Without a time limit nothing on the host depends on dt: never synchronise inside the loop, so launches queue
-    // ahead of the GPU.
+  // the time the host has to notice: the end of the run or the next output, whichever comes first
+  const bool open_ended = tlim < 0.0 && !(deadline < HUGE_VAL);
+  if (async_ok && open_ended) {
+    // Without a time limit or an output schedule nothing on the host depends on dt: never synchronise inside the loop, so
+    // launches queue ahead of the GPU.
     const long todo = cycles_left();
     if (todo < 0) throw std::runtime_error("no tlim, no nlim and no cycle budget: nothing bounds the run");
     run_async(todo);
   }
-  while (!(async_ok && tlim < 0.0) && (tlim < 0.0 || time < tlim) && (nlim < 0 || ncycle < nlim) &&
+  while (!(async_ok && open_ended) && !leave && (tlim < 0.0 || time < tlim) && (nlim < 0 || ncycle < nlim) &&
          (max_cycles < 0 || n < max_cycles)) {
     if (async_ok) {
       // With a time limit the host decides one thing only: when to stop.  SetGlobalTimeStep at most doubles dt, so k
       // cycles from here end no later than time + dt (2^k - 1): while that stays below tlim the loop condition holds
       // for every one of them whatever the estimates turn out to be, and they run as above (advance_dt applies the
-      // same rules, the tlim clamp included).  Close to tlim the cycles run one by one below.
+      // same rules, the tlim clamp included).  Close to tlim the cycles run one by one below.  The next output time
+      // bounds a batch the same way (no output can become due inside one) but is never passed to advance_dt.
       long k = 0;
-      const double room = (tlim - time) / dt;
+      const double lim = (tlim < 0.0) ? deadline : std::min(static_cast<double>(tlim), deadline);
+      const double room = (lim - time) / dt;
       while (k < 40 && std::ldexp(1.0, static_cast<int>(k)) * 1.001 < room) ++k; // time + dt 2^(k-1) < tlim, with a margin
       const long todo = cycles_left();
       if (todo >= 0) k = std::min(k, todo);
       if (k >= 2) {
         run_async(k);
+        outputs_due();
         continue;
       }
     }
@@ -3361,6 +3394,7 @@ long artemis_sim_impl::evolve(long max_cycles) {
     ndt = std::min(ndt, est);
     if (tlim > 0.0 && time < tlim && (tlim - time) < ndt) ndt = tlim - time;
     dt = ndt;
+    outputs_due();
   }
   for (void *g : gexec) artemis_rt_graph_destroy(g);
   fill_stale_ghosts(); // (inside the timed region: part of the work)
@@ -3412,6 +3446,50 @@ int artemis_sim_impl::history(double *out) {
             for (int q = 0; q < 3; ++q) out[6 + 4 * n + 1 + q] += d[(ns_dust + 3 * n + q) * N + c] * vv;
           }
         }
+  }
+  if (has_comm && nranks > 1 && comm.allreduce_sum(comm.ctx, out, nout)) throw std::runtime_error("allreduce failed");
+  return nout;
+}
+
+// The same integrals for every species, out = [mass, mom1..3, energy, internal energy] per gas species, then [mass,
+// mom1..3] per dust species: summed on the device from the primitives (kernels_history.hip; nothing is materialised or
+// downloaded but the sums), or -- a library without that kernel -- by history()'s host loop over all species.
+int artemis_sim_impl::history_device(double *out) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  const int nout = 6 * nsg + 4 * nsd;
+  for (int q = 0; q < nout; ++q) out[q] = 0.0;
+  if (artemis_hip_history_sums && artemis_hip_history_scratch_bytes) {
+    const artemis_pack_t p = make_pack(base);
+    if (!hist_sums.p) {
+      hist_sums.alloc(static_cast<size_t>(nout));
+      hist_scratch.alloc((artemis_hip_history_scratch_bytes(&p) + sizeof(double) - 1) / sizeof(double));
+    }
+    CK(artemis_hip_history_sums(&p, hist_sums.p, hist_scratch.p, stream), "history sums");
+    CK(artemis_rt_memcpy_d2h(out, hist_sums.p, static_cast<size_t>(nout) * sizeof(double), stream), "d2h");
+    CK(artemis_rt_stream_sync(stream), "sync");
+  } else {
+    materialise_cons();
+    for (int b = 0; b < nb; ++b) {
+      std::vector<Real> g, d;
+      if (nsg) g = download(gu0, b);
+      if (nsd) d = download(du0, b);
+      for (int k = ks; k <= ke; ++k)
+        for (int j = js; j <= je; ++j)
+          for (int i = is; i <= ie; ++i) {
+            const Real vv = cell_coords(b, k, j, i).volume();
+            const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
+            for (int n = 0; n < nsg; ++n) {
+              out[6 * n] += g[n * N + c] * vv;
+              for (int q = 0; q < 3; ++q) out[6 * n + 1 + q] += g[(nsg + 3 * n + q) * N + c] * vv;
+              out[6 * n + 4] += g[(4 * nsg + n) * N + c] * vv;
+              out[6 * n + 5] += g[(5 * nsg + n) * N + c] * vv;
+            }
+            for (int n = 0; n < nsd; ++n) {
+              out[6 * nsg + 4 * n] += d[n * N + c] * vv;
+              for (int q = 0; q < 3; ++q) out[6 * nsg + 4 * n + 1 + q] += d[(nsd + 3 * n + q) * N + c] * vv;
+            }
+          }
+    }
   }
   if (has_comm && nranks > 1 && comm.allreduce_sum(comm.ctx, out, nout)) throw std::runtime_error("allreduce failed");
   return nout;
@@ -3545,6 +3623,9 @@ struct artemis_sim {
   // A lean remesh releases the old state's work arrays BEFORE the new state allocates (peak = resident bytes); if the
   // new state then cannot be built or filled, the old one can no longer step: the handle is dead and says why
   std::string dead;
+  // the deck's <parthenon/output*> blocks once artemis_sim_enable_outputs or _outputs_describe has parsed them
+  // (outputs.cpp; it survives the remeshes of an adaptive run, which replace `p`)
+  artemis_out::State *outputs = nullptr;
 };
 
 // A fresh state for the same deck on a given set of leaves (the problem generator runs on it: tables, `ic` states
@@ -3839,6 +3920,24 @@ void finish_restore(artemis_sim_t *sim, const Meta &m, const std::vector<double>
 
 } // namespace artemis_ckpt
 
+// What outputs.cpp reaches of the handle (outputs_hooks.hpp)
+namespace artemis_out {
+
+Clock clock_of(const artemis_sim_t *sim) {
+  const artemis_sim_impl &S = *sim->p;
+  Clock c;
+  c.time = S.time, c.dt = S.dt, c.tlim = S.tlim, c.ncycle = S.ncycle, c.nlim = S.nlim, c.nblocks_global = S.nblocks_global;
+  c.ns_gas = S.do_gas ? S.ns_gas : 0, c.ns_dust = S.do_dust ? S.ns_dust : 0, c.rank = S.rank;
+  return c;
+}
+const std::string &deck_of(const artemis_sim_t *sim) { return sim->deck; }
+const std::vector<std::string> &overrides_of(const artemis_sim_t *sim) { return sim->overrides; }
+State *&state_of(artemis_sim_t *sim) { return sim->outputs; }
+const State *state_of(const artemis_sim_t *sim) { return sim->outputs; }
+int history_sums(artemis_sim_t *sim, double *out) { return sim->p->history_device(out); }
+
+} // namespace artemis_out
+
 extern "C" {
 
 const char *artemis_sim_last_error(void) { return g_sim_err.c_str(); }
@@ -3880,6 +3979,7 @@ void artemis_sim_destroy(artemis_sim_t *sim) {
   if (!sim) return;
   artemis_rt_device_sync();
   release_impl(sim->p);
+  artemis_out::destroy(sim->outputs);
   delete sim;
 }
 long artemis_sim_evolve(artemis_sim_t *sim, long max_cycles) {
@@ -3888,19 +3988,40 @@ long artemis_sim_evolve(artemis_sim_t *sim, long max_cycles) {
     g_sim_err = sim->dead;
     return -1;
   }
-  if (!(sim->p->adaptive && sim->p->refine_field)) {
+  const bool amr = sim->p->adaptive && sim->p->refine_field;
+  const bool outs = artemis_out::enabled(sim->outputs);
+  if (!amr && !outs) {
     GUARD(n = sim->p->evolve(max_cycles), return -1)
     return n;
   }
-  // adaptive mesh: one cycle at a time, a remesh check after each (the state object may be replaced)
+  // adaptive mesh: one cycle at a time, a remesh check after each (the state object may be replaced).
+  // Output schedule: a fresh run writes every block at cycle 0, once the first dt exists; the time loop writes history rows
+  // itself and returns when a dump is due, which is taken here, between two calls, like any other checkpoint; outputs
+  // follow the remesh of their cycle (parthenon's order: LoadBalancingAndAdaptiveMeshRefinement, then MakeOutputs).
+  auto ended = [&]() {
+    const artemis_sim_impl &S = *sim->p;
+    return !(S.tlim < 0.0 || S.time < S.tlim) || !(S.nlim < 0 || S.ncycle < S.nlim);
+  };
   auto run = [&]() {
     n = 0;
+    double wall = 0.0;
+    if (outs) {
+      sim->p->ensure_first_dt();
+      artemis_out::write_due(sim, false);
+    }
     while (max_cycles < 0 || n < max_cycles) {
-      const long k = sim->p->evolve(1);
+      const long k = amr ? sim->p->evolve(1) : sim->p->evolve(max_cycles < 0 ? -1 : max_cycles - n, sim);
+      wall += sim->p->last_wall;
       if (k <= 0) break;
       n += k;
-      remesh(*sim, false);
+      if (amr) remesh(*sim, false);
+      if (outs) {
+        artemis_out::write_due(sim, false);
+        if (ended()) break;
+      }
     }
+    if (outs && ended()) artemis_out::write_final(sim);
+    if (!amr) sim->p->last_wall = wall; // (the segments between two dumps add up to the run)
   };
   GUARD(run(), return -1)
   return n;
@@ -4060,6 +4181,15 @@ int artemis_sim_get_field(artemis_sim_t *s, const char *field, int block, double
 int artemis_sim_history(artemis_sim_t *s, double *out) {
   int n = -1;
   GUARD(n = s->p->history(out), return -1)
+  return n;
+}
+int artemis_sim_history_device(artemis_sim_t *s, double *out) {
+  int n = -1;
+  if (!s->dead.empty()) {
+    g_sim_err = s->dead;
+    return -1;
+  }
+  GUARD(n = s->p->history_device(out), return -1)
   return n;
 }
 int artemis_sim_errors(artemis_sim_t *s, double *out) {

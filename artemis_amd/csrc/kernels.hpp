@@ -115,4 +115,7 @@ void launch_ml_restrict_halos(const PackView &P, const artemis_ml_pack_t &ml, co
 void launch_ml_prolongate(const PackView &P, const artemis_ml_pack_t &ml, const artemis_ml_box_t *boxes, int nboxes,
                           hipStream_t s);
 void launch_ml_floor_ghosts(const PackView &P, const int *blocks, int nblocks, hipStream_t s);
+// kernels_history.hip: rows of partial sums the first launch writes (a function of the pack's shape alone)
+long history_workgroups(const PackView &P);
+void launch_history_sums(const PackView &P, double *sums, double *scratch, hipStream_t s);
 } // namespace artemis

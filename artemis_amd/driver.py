@@ -252,6 +252,9 @@ def _declare(L):
     L.artemis_sim_checkpoint_describe.argtypes = [C.c_char_p, C.c_char_p, l]
     L.artemis_sim_checkpoint_seconds.argtypes = [C.POINTER(d)]
     L.artemis_sim_checkpoint_seconds.restype = None
+    L.artemis_sim_enable_outputs.argtypes = [vp, C.c_char_p]
+    L.artemis_sim_history_device.argtypes = [vp, C.POINTER(d)]
+    L.artemis_sim_outputs_describe.argtypes = [vp, C.c_char_p, l]
     L._sim_declared = True
 
 
@@ -463,6 +466,33 @@ class Simulation:
         if n < 0:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
         return np.array(o[:n])
+
+    def history_device(self):
+        """The history integrals of every species, summed on the device from the primitives and reduced over the ranks:
+        [mass, mom1..3, energy, internal energy] per gas species, then [mass, mom1..3] per dust species."""
+        o = (C.c_double * max(6 * self.ns_gas + 4 * self.ns_dust, 1))()
+        n = self.L.artemis_sim_history_device(self.h, o)
+        if n < 0:
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+        return np.array(o[:n])
+
+    def enable_outputs(self, directory):
+        """Act on the deck's <parthenon/outputN> blocks from now on: `hst` blocks append rows to
+        <directory>/<problem_id>.outN.hst (artemis_amd.history.read_history reads them), `rst` blocks save checkpoints to
+        <directory>/<problem_id>.outN.<counter>.rst (Simulation.restore reads them).  Output times never change dt."""
+        if self.L.artemis_sim_enable_outputs(self.h, os.fspath(directory).encode()):
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+
+    def outputs(self):
+        """The deck's output blocks and their state (status, next_time, rows or dumps written) as a dict."""
+        import json
+        n = self.L.artemis_sim_outputs_describe(self.h, None, 0)
+        if n < 0:
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+        buf = C.create_string_buffer(n + 1)
+        if self.L.artemis_sim_outputs_describe(self.h, buf, n + 1) != n:
+            raise RuntimeError("the output state changed while it was read")
+        return json.loads(buf.value.decode())
 
     def errors(self):
         o = (C.c_double * 16)()

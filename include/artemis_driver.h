@@ -170,7 +170,8 @@ int artemis_sim_errors(artemis_sim_t *sim, double *out);
  * and the remesh history of an adaptive mesh, the n-body force sums, and per block the whole primitive arrays, ghost zones
  * included, bytes as they are.  Everything else is rebuilt from the deck.  A restored run continues bit for bit like the
  * run that was saved, on any number of ranks (n-body sums regroup across rank counts: equal to round-off there).
- * Callers checkpoint between artemis_sim_evolve calls; the <parthenon/output*> blocks of a deck are not acted on.
+ * Callers checkpoint between artemis_sim_evolve calls, or let the deck's `rst` output blocks do it ("deck-driven
+ * outputs" below).
  *
  * save: collective over the ranks of the simulation, which must see one file system.  Writes <path>.tmp and renames it
  * once every rank has succeeded (an existing checkpoint at <path> is replaced).  Returns 0, non-zero on error. */
@@ -188,6 +189,32 @@ int artemis_sim_checkpoint_describe(const char *path, char *json_out, long capac
 /* Wall-clock seconds of the calling thread's last save or restore: out4 = {total (a restore: building the state from the
  * deck included), device copies, checksums, file writes or reads}. */
 void artemis_sim_checkpoint_seconds(double *out4);
+
+/* ---- deck-driven outputs ---------------------------------------------------------------------------------------------
+ * The <parthenon/outputN> blocks of the deck (file_type, dt) are acted on only after artemis_sim_enable_outputs; without
+ * it artemis_sim_evolve writes nothing.  Files go to `dir` (created if missing; the ranks must see one file system):
+ *   file_type = hst   <dir>/<problem_id>.outN.hst: "#  History data", a label line "# [1]=time [2]=dt [3]=cycle
+ *                     [4]=nbtotal [5]=gas_mass_0 ..." (gas_mass_n, gas_momentum_x{1,2,3}_n, gas_energy_n,
+ *                     gas_internal_energy_n, dust_mass_n, dust_momentum_x{1,2,3}_n; the species is the inner index), then
+ *                     one row per output, floats as %.16e.  time, dt, cycle are the clock after the cycle (dt: the next
+ *                     step's).  An existing file is appended to behind a fresh header section.  Rank 0 writes.
+ *   file_type = rst   artemis_sim_save into <dir>/<problem_id>.outN.<5-digit counter>.rst, and into ...outN.final.rst
+ *                     when the run ends.
+ *   anything else     not acted on (never an error); artemis_sim_outputs_describe lists it as skipped.
+ * Schedule (parthenon's Outputs, upstream): a block is due after the first cycle that ends with time >= next_time, and
+ * next_time then becomes the smallest integer multiple of the block's dt above time; a fresh run writes every block at
+ * cycle 0 (once the first dt exists); every block is written once more when the run ends at tlim or nlim -- not when a
+ * max_cycles budget runs out, and not twice for one cycle.  A restored run derives next_time from its clock.  Output times
+ * never clip dt: the run takes the same steps with and without outputs.  Returns 0, non-zero on error. */
+int artemis_sim_enable_outputs(artemis_sim_t *sim, const char *dir);
+/* The history integrals of every species, summed on the device from the primitives (artemis_hip_history_sums) and reduced
+ * over the ranks: out = [mass, mom1..3, energy, internal energy] per gas species, then [mass, mom1..3] per dust species
+ * (the layout of artemis_sim_history for one gas species).  Returns the number of values, < 0 on error. */
+int artemis_sim_history_device(artemis_sim_t *sim, double *out);
+/* The output blocks of the deck and their state as one JSON object {"enabled", "dir", "problem_id", "blocks": [{"block",
+ * "index", "file_type", "dt", "status", "next_time", "written", "last_cycle", "path"}]}.  Returns the length of the text
+ * (written with its NUL only if capacity exceeds it: call with NULL / 0 for the size), < 0 on error. */
+int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long capacity);
 
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured

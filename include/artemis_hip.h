@@ -225,6 +225,17 @@ int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, doub
 int artemis_hip_estimate_dt_async(const artemis_pack_t *p, int fluid, double cfl, double *dt_dev,
                                   void *stream);
 
+/* History integrals (utils/history.hpp:29-100; gas.cpp:648-676, dust.cpp:332-352) from p's PRIMITIVES: the conserved
+ * value of every interior zone is formed in registers with PrimToCons's expressions and operation order (floors included)
+ * and multiplied by Coords::Volume(); no conserved array is read or written.  sums_dev (DEVICE) receives
+ * 6 * gas.nspecies + 4 * dust.nspecies doubles: per gas species [mass, mom1, mom2, mom3, total energy, internal energy],
+ * then per dust species [mass, mom1, mom2, mom3].  scratch_dev: DEVICE scratch of artemis_hip_history_scratch_bytes(p)
+ * bytes (one row of partial sums per workgroup; a second launch adds the rows in index order).  The number of rows
+ * depends on the pack's shape only and nothing is combined with atomics: the same state gives the same bits on every
+ * run and every device.  Asynchronous on `stream`. */
+size_t artemis_hip_history_scratch_bytes(const artemis_pack_t *p);
+int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_dev, double *scratch_dev, void *stream);
+
 /* Metric tables.  geometry::Coords<GEOM> evaluates transcendentals per cell: for spherical 2-D/3-D
  * cos/sin of the x2 faces, the x2 centroid and the x2 midpoint (spherical.hpp:61-146); for
  * ConvertCoordsToCart (used by Coords::Distance in the diffusion tasks) cos/sin of the azimuth of
