@@ -224,6 +224,7 @@ def load():
         "artemis_hip_cooling_table_fill": (i, [PPk, vp, vp, C.POINTER(Cooling), i, vp, vp]),
         "artemis_hip_stage_fused": (i, [PPk, C.POINTER(StageArgs), vp]),
         "artemis_hip_stage_fused_redo_shell": (i, [PPk, C.POINTER(StageArgs), vp]),
+        "artemis_hip_redo_totals": (i, [C.POINTER(C.c_ulonglong), i]),
         "artemis_hip_stage_general": (i, [PPk, C.POINTER(StageGeneralArgs), vp]),
         "artemis_hip_stage_general_variant": (i, [PPk, C.POINTER(StageGeneralArgs)]),
         "artemis_hip_stage_general_dust_variant": (i, [PPk, C.POINTER(StageGeneralArgs)]),
@@ -311,7 +312,7 @@ EXPORTS_HIP = [
     "artemis_hip_set_aux", "artemis_hip_cons_to_prim", "artemis_hip_prim_to_cons", "artemis_hip_prim_to_cons_ghosts",
     "artemis_hip_deep_copy_conserved", "artemis_hip_estimate_dt", "artemis_hip_estimate_dt_async",
     "artemis_hip_history_scratch_bytes", "artemis_hip_history_sums",
-    "artemis_hip_apply_bc", "artemis_hip_stage_fused", "artemis_hip_stage_fused_redo_shell", "artemis_hip_metric_count",
+    "artemis_hip_apply_bc", "artemis_hip_stage_fused", "artemis_hip_stage_fused_redo_shell", "artemis_hip_redo_totals", "artemis_hip_metric_count",
     "artemis_hip_metric_fill", "artemis_hip_external_gravity", "artemis_hip_nbody_gravity", "artemis_hip_nbody_force_scratch",
     "artemis_hip_nbody_force_sums", "artemis_hip_timestep_all", "artemis_hip_redo_scratch_bytes", "artemis_hip_rotating_frame_force",
     "artemis_hip_ml_exchange", "artemis_hip_ml_flux_correction", "artemis_hip_ml_restrict_halos", "artemis_hip_ml_prolongate",
@@ -344,6 +345,14 @@ def object_sha(unit):
 def check(rc):
     if rc != 0:
         raise ArtemisHipError(rc, load().artemis_hip_last_error().decode())
+
+
+def redo_totals(reset=False):
+    """(bulk, shell): zones the redo kernel has recomputed on the current device since the last reset
+    (artemis_hip_redo_totals; waits for the device)."""
+    out = (C.c_ulonglong * 2)()
+    check(load().artemis_hip_redo_totals(out, 1 if reset else 0))
+    return int(out[0]), int(out[1])
 
 
 import contextlib

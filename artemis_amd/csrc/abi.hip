@@ -761,6 +761,11 @@ int artemis_hip_stage_fused_redo_shell(const artemis_pack_t *p, const artemis_st
   artemis::launch_stage_fused_redo_shell(artemis::make_pack_view(*p), *a, p->gas.riemann, recon, S(stream));
   return after_launch("stage_fused_redo_shell");
 }
+int artemis_hip_redo_totals(unsigned long long *totals, int reset) {
+  if (!totals) return fail(ARTEMIS_HIP_EINVAL, "redo totals: null output");
+  if (artemis::redo_totals(totals, reset)) return fail(ARTEMIS_HIP_EDEVICE, "redo totals: the device copy failed");
+  return ARTEMIS_HIP_OK;
+}
 
 // Diffusion guards shared by the four tasks (see include/artemis_hip.h for what is built)
 static int validate_diffusion(const artemis_pack_t *p, const artemis_diffusion_t *d, bool need_flux) {

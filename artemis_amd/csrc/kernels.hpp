@@ -46,6 +46,7 @@ void launch_wait_counter(unsigned *counter, unsigned target, unsigned *timeout_f
 int launch_stage_fused(const PackView &P, const artemis_stage_args_t &a, int riemann, int recon,
                        hipStream_t s);
 int launch_stage_fused_redo_shell(const PackView &P, const artemis_stage_args_t &a, int riemann, int recon, hipStream_t s);
+int redo_totals(unsigned long long *out, int reset);
 bool fused_flux_covers(const PackView &P, int recon);
 int launch_flux_fused(const PackView &P, int riemann, int recon, hipStream_t s);
 void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args_t &g, const StagePlan &pl, int riemann_gas,

@@ -22,6 +22,7 @@
 //     Pressure of stencil cells is likewise recomputed as (gm1*rho)*sie.
 // HBM traffic per cell-stage: 5 reads (+5 for u1 after stage 1) + 6 writes instead of the
 // reference's ~124 doubles.  Results are bit-identical to the per-task kernels.
+#ifndef ARTEMIS_FUSED_LEAN_PASS // (the file includes itself once for the lean kernel: see STAGE_KERNEL_HEAD)
 #include <algorithm>
 #include <cfloat>
 #include <cstdlib>
@@ -208,13 +209,46 @@ ADEV void put6(double (*A)[QY][QX], int r, int c, const Cell6 &q) {
   A[0][r][c] = q.d, A[1][r][c] = q.v1, A[2][r][c] = q.v2;
   A[3][r][c] = q.v3, A[4][r][c] = q.p, A[5][r][c] = q.e;
 }
+ADEV void put5(double (*A)[QY][QX], int r, int c, const Cell6 &q) {
+  A[0][r][c] = q.d, A[1][r][c] = q.v1, A[2][r][c] = q.v2;
+  A[3][r][c] = q.v3, A[4][r][c] = q.p;
+}
 // (GET6 / PUT8 / GET8, FOR6: march_device.hpp)
+#define FOR5(X) X(d, 0) X(v1, 1) X(v2, 2) X(v3, 3) X(p, 4)
+// The lean form of the Cartesian stage (LEAN) carries no second energy equation: a cell has no
+// `e` slot in LDS and a face no `eg` / `vf` slot.  The members nobody stores get a constant.
+#define GET6L(dst, A, ...)                                                                 \
+  if constexpr (LEAN) {                                                                    \
+    GET6(4, dst, A, __VA_ARGS__);                                                          \
+    dst.p = A[4] __VA_ARGS__, dst.e = 0.0;                                                 \
+  } else {                                                                                 \
+    GET6(6, dst, A, __VA_ARGS__);                                                          \
+  }
+#define PUT8L(A, fl, ...)                                                                  \
+  if constexpr (LEAN) {                                                                    \
+    PUT8(4, A, fl, __VA_ARGS__);                                                           \
+    A[4] __VA_ARGS__ = fl.e, A[6] __VA_ARGS__ = fl.pf;                                     \
+  } else {                                                                                 \
+    PUT8(6, A, fl, __VA_ARGS__);                                                           \
+  }
+#define GET8L(fl, A, ...)                                                                  \
+  if constexpr (LEAN) {                                                                    \
+    GET8(4, fl, A, __VA_ARGS__);                                                           \
+    fl.e = A[4] __VA_ARGS__, fl.pf = A[6] __VA_ARGS__, fl.eg = 0.0, fl.vf = 0.0;           \
+  } else {                                                                                 \
+    GET8(6, fl, A, __VA_ARGS__);                                                           \
+  }
 
 // Stage one plane's primitives (own cell + this thread's halo cell) into S.Q.
-template <class TILE>
+template <bool LEAN = false, class TILE>
 ADEV void stage_plane(TILE &S, const Ctx &x, const Cell6 &q, const Raw5 &hal) {
-  put6(S.Q, x.ty + FH, x.tx + FH, q);
-  if (x.hr >= 0) put6(S.Q, x.hr, x.hc, finish_cell(hal, x.gm1));
+  if constexpr (LEAN) {
+    put5(S.Q, x.ty + FH, x.tx + FH, q);
+    if (x.hr >= 0) put5(S.Q, x.hr, x.hc, finish_cell(hal, x.gm1));
+  } else {
+    put6(S.Q, x.ty + FH, x.tx + FH, q);
+    if (x.hr >= 0) put6(S.Q, x.hr, x.hc, finish_cell(hal, x.gm1));
+  }
 }
 // Guarded tiles (the curvilinear kernel and the flux task) note whether the plane they stage (parity `par`) holds a
 // velocity the hand-scheduled divisions cannot take (geometry.hpp: tiny_nonzero -- ahead of a shock velocities decay
@@ -241,7 +275,9 @@ ADEV bool tiny_v(const Cell6 &q) { return tiny_vel3(q.v1, q.v2, q.v3); }
 // wave (and no SIMD) carries the extra Riemann pass every plane.
 // DETECT (the Cartesian stage): the plane flags are kept but every division stays hand-scheduled; `flagged` tells the
 // caller that this plane's tile (halo included) holds a tiny velocity, so that the zones concerned are redone exactly.
-template <int RIEMANN, int RECON, bool D3, bool CURV, bool GUARD, bool DETECT, class TILE>
+// LEAN (the lean form of the Cartesian stage): nothing of the internal-energy equation -- no `e` slope, no Q[5] / [5]
+// slot of a face value, no eg / vf slot of a face flux.
+template <int RIEMANN, int RECON, bool D3, bool CURV, bool GUARD, bool DETECT, bool LEAN, class TILE>
 ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CURV> &gx, const int k,
                        const Cell6 &qc, const bool stage_next, const Cell6 &qn, const Raw5 &hal_next,
                        Flux8 &fx_lo, Flux8 &fy_lo, bool &flagged, const bool det FPROF_ARGS) {
@@ -272,13 +308,15 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   if (t >= 64) __builtin_amdgcn_s_setprio(2);
 #endif
   // ---- P1: slopes of the own cell; perimeter slopes on waves 2 (x1) and 3 (x2) -----------
+  constexpr int NQ = LEAN ? 5 : 6; // variables a cell has in LDS
   Cell6 lox, loy;
+  if constexpr (LEAN) lox.e = loy.e = 0.0;
   double xm_[6], xp_[6], ym_[6], yp_[6]; // the own cell's neighbours of both directions: 24 reads in flight at once
 #pragma unroll
-  for (int n = 0; n < 6; ++n) xm_[n] = S.Q[n][ty + FH][tx + FH - 1], xp_[n] = S.Q[n][ty + FH][tx + FH + 1];
+  for (int n = 0; n < NQ; ++n) xm_[n] = S.Q[n][ty + FH][tx + FH - 1], xp_[n] = S.Q[n][ty + FH][tx + FH + 1];
   if (multi_d) {
 #pragma unroll
-    for (int n = 0; n < 6; ++n) ym_[n] = S.Q[n][ty + FH - 1][tx + FH], yp_[n] = S.Q[n][ty + FH + 1][tx + FH];
+    for (int n = 0; n < NQ; ++n) ym_[n] = S.Q[n][ty + FH - 1][tx + FH], yp_[n] = S.Q[n][ty + FH + 1][tx + FH];
   }
   if constexpr (GUARD) flagged = (flag_ != 0), fastp = !flagged;
   double ux_[6], uy_[6]; // upper face values: stored after the last slope
@@ -298,10 +336,10 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   }
 #define FLAT6(lm, rm)                                                                      \
   (fastp && __all(plm_flat(lm[0], qc.d, rm[0]) && plm_flat(lm[1], qc.v1, rm[1]) && plm_flat(lm[2], qc.v2, rm[2]) && \
-                  plm_flat(lm[3], qc.v3, rm[3]) && plm_flat(lm[4], qc.p, rm[4]) && plm_flat(lm[5], qc.e, rm[5])))
+                  plm_flat(lm[3], qc.v3, rm[3]) && plm_flat(lm[4], qc.p, rm[4]) && (LEAN || plm_flat(lm[5], qc.e, rm[5]))))
 #define SLX(m, n, F) SLOPE(m, n, xm_, xp_, lox, ux_, gx.g1, F)
 #define SLY(m, n, F) SLOPE(m, n, ym_, yp_, loy, uy_, gx.g2, F)
-#define SL6(S, F) S(d, 0, F) S(v1, 1, F) S(v2, 2, F) S(v3, 3, F) S(p, 4, F) S(e, 5, F)
+#define SL6(S, F) S(d, 0, F) S(v1, 1, F) S(v2, 2, F) S(v3, 3, F) S(p, 4, F) if constexpr (!LEAN) S(e, 5, F)
   if constexpr (SK6) {
     if (FLAT6(xm_, xp_)) { SL6(SLX, true) } else { SL6(SLX, false) }
     if (multi_d) {
@@ -317,10 +355,10 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
 #undef FLAT6
 #undef SLOPE
 #pragma unroll
-  for (int n = 0; n < 6; ++n) S.UPX[n][ty][tx + 1] = ux_[n];
+  for (int n = 0; n < NQ; ++n) S.UPX[n][ty][tx + 1] = ux_[n];
   if (multi_d) {
 #pragma unroll
-    for (int n = 0; n < 6; ++n) S.UPY[n][ty + 1][tx] = uy_[n];
+    for (int n = 0; n < NQ; ++n) S.UPY[n][ty + 1][tx] = uy_[n];
   }
   if constexpr (GUARD || DETECT) { // set again when the next plane is staged (after the barrier); behind the reads above
     if ((GUARD || det) && x.t == 0) tiny_flag(S, (k + 1) & 1) = 0;
@@ -332,10 +370,10 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   bool flat_ = false;                                                                      \
   if constexpr (SK6) {                                                                     \
     bool f_ = true;                                                                        \
-    _Pragma("unroll") for (int n = 0; n < 6; ++n) f_ = f_ && plm_flat(pm_[n], pc_[n], pp_[n]); \
+    _Pragma("unroll") for (int n = 0; n < NQ; ++n) f_ = f_ && plm_flat(pm_[n], pc_[n], pp_[n]); \
     flat_ = fastp && __all(f_);                                                            \
   }                                                                                        \
-  _Pragma("unroll") for (int n = 0; n < 6; ++n) {                                          \
+  _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                         \
     double up_, lo_;                                                                       \
     if constexpr (PG) {                                                                    \
       if (fastp) plm_g_shared<2>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                   \
@@ -351,11 +389,11 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
     const int cx = side ? FTX + FH : FH - 1;
     double pm_[6], pc_[6], pp_[6], po_[6];
 #pragma unroll
-    for (int n = 0; n < 6; ++n)
+    for (int n = 0; n < NQ; ++n)
       pm_[n] = S.Q[n][row + FH][cx - 1], pc_[n] = S.Q[n][row + FH][cx], pp_[n] = S.Q[n][row + FH][cx + 1];
     DUTY_SLOPES(S.GX1[side])
 #pragma unroll
-    for (int n = 0; n < 6; ++n) {
+    for (int n = 0; n < NQ; ++n) {
       if (side) S.LOX[n][row] = po_[n];
       else S.UPX[n][row][0] = po_[n];
     }
@@ -365,11 +403,11 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
     const int ry = side ? FTY + FH : FH - 1;
     double pm_[6], pc_[6], pp_[6], po_[6];
 #pragma unroll
-    for (int n = 0; n < 6; ++n)
+    for (int n = 0; n < NQ; ++n)
       pm_[n] = S.Q[n][ry - 1][cx + FH], pc_[n] = S.Q[n][ry][cx + FH], pp_[n] = S.Q[n][ry + 1][cx + FH];
     DUTY_SLOPES(S.GX2[side][cx])
 #pragma unroll
-    for (int n = 0; n < 6; ++n) {
+    for (int n = 0; n < NQ; ++n) {
       if (side) S.LOY[n][cx] = po_[n];
       else S.UPY[n][0][cx] = po_[n];
     }
@@ -384,17 +422,17 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   // solves and requests its states there: ahead of them it holds both left states through a third solver pass and the
   // stage-2 kernels spill (48 - 64 bytes of scratch with all three of HLLC, HLLE, LLF).
   Cell6 L, L2;
-  GET6(6, L, S.UPX, [ty][tx]);
+  GET6L(L, S.UPX, [ty][tx])
   L2 = L;
-  if (multi_d) { GET6(6, L2, S.UPY, [ty][tx]); }
+  if (multi_d) { GET6L(L2, S.UPY, [ty][tx]) }
   fx_lo = solve_face<RIEMANN, 1, SKF>(x.gk, L, lox, fastp);
   if constexpr (CURV) fx_lo.m2 *= gx.h1[1], fx_lo.m3 *= gx.h1[2]; // ScaleMomentumFlux (h1 == 1)
-  if (tx > 0) { PUT8(6, S.FX, fx_lo, [ty][tx - 1]); }
+  if (tx > 0) { PUT8L(S.FX, fx_lo, [ty][tx - 1]) }
   fy_lo = fx_lo;
   if (multi_d) {
     fy_lo = solve_face<RIEMANN, 2, SKF>(x.gk, L2, loy, fastp);
     if constexpr (CURV) fy_lo.m2 *= gx.h2[1], fy_lo.m3 *= gx.h2[2];
-    if (ty > 0) { PUT8(6, S.FY, fy_lo, [ty - 1][tx]); }
+    if (ty > 0) { PUT8L(S.FY, fy_lo, [ty - 1][tx]) }
   }
   if (t >= 64 && t < 128) { // lanes 0..7: x1 face i0+32 per row; lanes 32..63: x2 face j0+8
     // ONE Riemann pass for both kinds of perimeter face (march_device.hpp rotate_x2_in / _out), so the duty wave runs
@@ -405,21 +443,21 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
       const int cx = u - 32;
       Cell6 l, r;
       if (isx) {
-        GET6(6, l, S.UPX, [u][FTX]);
-        GET6(6, r, S.LOX, [u]);
+        GET6L(l, S.UPX, [u][FTX])
+        GET6L(r, S.LOX, [u])
       } else {
-        GET6(6, l, S.UPY, [FTY][cx]);
-        GET6(6, r, S.LOY, [cx]);
+        GET6L(l, S.UPY, [FTY][cx])
+        GET6L(r, S.LOY, [cx])
         rotate_x2_in(l), rotate_x2_in(r);
       }
       Flux8 fe_ = solve_face<RIEMANN, 1, SKF>(x.gk, l, r, fastp);
       if (isx) {
         if constexpr (CURV) fe_.m2 *= S.HF1[u][0], fe_.m3 *= S.HF1[u][1]; // the face below cell (j0+u, i0+32)
-        PUT8(6, S.FX, fe_, [u][FTX - 1]);
+        PUT8L(S.FX, fe_, [u][FTX - 1])
       } else {
         rotate_x2_out(fe_);
         if constexpr (CURV) fe_.m2 *= S.HF2[cx][0], fe_.m3 *= S.HF2[cx][1]; // the face below cell (j0+8, i0+cx)
-        PUT8(6, S.FY, fe_, [FTY - 1][cx]);
+        PUT8L(S.FY, fe_, [FTY - 1][cx])
       }
     }
   }
@@ -428,7 +466,7 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
 #endif
   FPROF(9);
   if (stage_next) {
-    stage_plane(S, x, qn, hal_next);
+    stage_plane<LEAN>(S, x, qn, hal_next);
     if constexpr (GUARD || DETECT) {
       if (GUARD || det) stage_plane_flag(S, x, qn, hal_next, (k + 1) & 1);
     }
@@ -491,7 +529,10 @@ ADEV void redo_append(const StageK &a, const PackView &P, int b, unsigned c, boo
   if (at < a.redo_cap)
     list[at] = static_cast<unsigned long long>(b) * (static_cast<unsigned long long>(P.nk) * P.nj * P.ni) + static_cast<unsigned long long>(c);
 }
-template <bool HAS_U1, bool WRITE_CONS, bool WITH_DT, bool D3, class TILE>
+// LEAN: the internal-energy equation (G: ApplyUpdate of cons::internal_energy and FluxSource's p div v) is left out.
+// SetAuxillaryFields reads G only where the total-energy update leaves no usable internal energy (!(ue > de_switch * E));
+// such a zone goes to the redo list as well, whose kernel computes G.  Launched only with a redo list.
+template <bool HAS_U1, bool WRITE_CONS, bool WITH_DT, bool D3, bool LEAN, class TILE>
 ADEV void plane_update(TILE &S, const PackView &P, const StageK &a, const Ctx &x, const int k,
                        const Cell6 &qc, const Flux8 &fx_lo, const Flux8 &fy_lo, const Flux8 &fz_lo,
                        const Flux8 &fz_hi, const Raw5 &u1raw, double &ldt, const bool bad_in, const bool shell_wg) {
@@ -501,8 +542,8 @@ ADEV void plane_update(TILE &S, const PackView &P, const StageK &a, const Ctx &x
   const double gm1 = x.gm1;
   const FluidView &f = P.gas;
   Flux8 fx_hi, fy_hi = fx_lo;
-  GET8(6, fx_hi, S.FX, [ty][tx]);
-  if (multi_d) { GET8(6, fy_hi, S.FY, [ty][tx]); }
+  GET8L(fx_hi, S.FX, [ty][tx])
+  if (multi_d) { GET8L(fy_hi, S.FY, [ty][tx]) }
   if (!x.active) return;
   const double *g = x.g + opaque(4); // (scalar loads at their use: fused_device.hpp kload)
   const double dx1 = x.dx1, dx2 = x.dx2;
@@ -540,18 +581,20 @@ ADEV void plane_update(TILE &S, const PackView &P, const StageK &a, const Ctx &x
   double M2 = upd(M20, M21, fx_lo.m2, fx_hi.m2, fy_lo.m2, fy_hi.m2, fz_lo.m2, fz_hi.m2);
   double M3 = upd(M30, M31, fx_lo.m3, fx_hi.m3, fy_lo.m3, fy_hi.m3, fz_lo.m3, fz_hi.m3);
   const double E = upd(E0, E1, fx_lo.e, fx_hi.e, fy_lo.e, fy_hi.e, fz_lo.e, fz_hi.e);
-  double G = upd(G0, G1, fx_lo.eg, fx_hi.eg, fy_lo.eg, fy_hi.eg, fz_lo.eg, fz_hi.eg);
+  double G = 0.0;
+  if constexpr (!LEAN) G = upd(G0, G1, fx_lo.eg, fx_hi.eg, fy_lo.eg, fy_hi.eg, fz_lo.eg, fz_hi.eg);
   // FluxSource (fluid_fluxes.hpp:365-392)
-  const double bdt_vol = div(x.bdt, rvol);
+  double bdt_vol = 0.0;
+  if constexpr (!LEAN) bdt_vol = div(x.bdt, rvol);
   M1 += div(x.bdt, x.rdx1) * (fx_lo.pf - fx_hi.pf);
-  G -= bdt_vol * 0.5 * (fx_lo.pf + fx_hi.pf) * (ax1 * fx_hi.vf - ax1 * fx_lo.vf);
+  if constexpr (!LEAN) G -= bdt_vol * 0.5 * (fx_lo.pf + fx_hi.pf) * (ax1 * fx_hi.vf - ax1 * fx_lo.vf);
   if (multi_d) {
     M2 += div(x.bdt, x.rdx2) * (fy_lo.pf - fy_hi.pf);
-    G -= bdt_vol * 0.5 * (fy_lo.pf + fy_hi.pf) * (ax2 * fy_hi.vf - ax2 * fy_lo.vf);
+    if constexpr (!LEAN) G -= bdt_vol * 0.5 * (fy_lo.pf + fy_hi.pf) * (ax2 * fy_hi.vf - ax2 * fy_lo.vf);
   }
   if (three_d) {
     M3 += div(x.bdt, rdx3) * (fz_lo.pf - fz_hi.pf);
-    G -= bdt_vol * 0.5 * (fz_lo.pf + fz_hi.pf) * (ax3 * fz_hi.vf - ax3 * fz_lo.vf);
+    if constexpr (!LEAN) G -= bdt_vol * 0.5 * (fz_lo.pf + fz_hi.pf) * (ax3 * fz_hi.vf - ax3 * fz_lo.vf);
   }
   // SetAuxillaryFields (fill_derived.cpp:54-73, artemis_utils.hpp:43-62) and ConsToPrim
   // (fill_derived.cpp:137-151) divide six times by the same floored density.  Not plane_update_curv's form: every
@@ -559,16 +602,23 @@ ADEV void plane_update(TILE &S, const PackView &P, const StageK &a, const Ctx &x
   // would need the IEEE fallback -- another expression set.
   const double w_d = (D > f.dfloor) ? D : f.dfloor; // == max(D, dfloor) of artemis_utils.hpp:49
   const Recip rd = recip(w_d);
+  [[maybe_unused]] bool need_g = false; // LEAN: the select below would take G (the negated comparison: a NaN takes G too)
   {
     const double ke = div(0.5 * (sqr(M1 / 1.0) + sqr(M2 / 1.0) + sqr(M3 / 1.0)), rd);
     const double ue = E - ke;
-    double sie = div((ue > f.de_switch * E) ? ue : G, rd);
+    double sie;
+    if constexpr (LEAN) {
+      need_g = !(ue > f.de_switch * E);
+      sie = div(ue, rd);
+    } else {
+      sie = div((ue > f.de_switch * E) ? ue : G, rd);
+    }
     sie = amax(sie, f.siefloor);
     G = sie * w_d;
     const double uflr = f.siefloor * w_d;
     G = (G > uflr) ? G : uflr;
   }
-  if (a.redo_cnt0 && (bad_in || tiny_mom3(M1, M2, M3))) {
+  if (a.redo_cnt0 && (bad_in || need_g || tiny_mom3(M1, M2, M3))) {
     redo_append(a, P, b, c, shell_wg);
     return;
   }
@@ -770,9 +820,28 @@ ADEV void plane_update_curv(TILE &S, const PackView &P, const StageK &a, const S
   if constexpr (WITH_DT) ldt = amin(ldt, zone_dt_term(w_d, n1, n2, n3, w_s, rwd, x.gm1, co, multi_d, three_d));
 }
 
-template <int RIEMANN, int RECON, bool HAS_U1, bool WRITE_CONS, bool WITH_DT, bool D3, bool CURV = false, bool FLUXES = false>
-__global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stage_fused_kernel(const PackView P, const StageK a,
-                                                                       const SrcArg<CURV> src) {
+// The kernel's text is compiled twice: as stage_fused_kernel, and -- this file includes itself
+// once, below the kernel, with ARTEMIS_FUSED_LEAN_PASS defined -- as stage_fused_kernel_lean, the lean form of the
+// Cartesian stage: the same march without the internal-energy equation, for launches with a redo list.  A second kernel
+// and not a ninth template parameter or a shared body function: the instantiations of stage_fused_kernel keep their
+// names and their assembly (a body inlined from a function loads the kernel arguments differently).
+#define STAGE_KERNEL_HEAD                                                                                               \
+  template <int RIEMANN, int RECON, bool HAS_U1, bool WRITE_CONS, bool WITH_DT, bool D3, bool CURV = false, bool FLUXES = false> \
+  __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stage_fused_kernel(const PackView P, const StageK a, \
+                                                                                                 const SrcArg<CURV> src)
+#define STAGE_KERNEL_FLAGS constexpr bool LEAN = false;
+#else // ARTEMIS_FUSED_LEAN_PASS: the second pass over the kernel's text
+// (the same parameters, so that the text reads the same: the flux task stores eg / vf and the curvilinear march has no
+//  redo list -- neither has a lean form)
+#define STAGE_KERNEL_HEAD                                                                                               \
+  template <int RIEMANN, int RECON, bool HAS_U1, bool WRITE_CONS, bool WITH_DT, bool D3, bool CURV = false, bool FLUXES = false> \
+  __global__ __launch_bounds__(NT, 2) void stage_fused_kernel_lean(const PackView P, const StageK a, const SrcArg<CURV> src)
+#define STAGE_KERNEL_FLAGS     \
+  constexpr bool LEAN = true;  \
+  static_assert(!CURV && !FLUXES, "the lean form: the Cartesian stage only");
+#endif
+STAGE_KERNEL_HEAD {
+  STAGE_KERNEL_FLAGS
   __shared__ std::conditional_t<CURV, LdsTileCurv, LdsTile> S;
   Ctx x;
   x.tx = threadIdx.x, x.ty = threadIdx.y, x.t = x.ty * FTX + x.tx;
@@ -924,13 +993,13 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
     fz.d = fz.m1 = fz.m2 = fz.m3 = fz.e = fz.eg = fz.pf = fz.vf = 0.0;
     Raw5 hal = u1raw;
     if (x.hr >= 0) hal = load_raw(x.in_r, x.in_1, x.in_2, x.in_3, x.in_e, x.hcol + k0 * x.sk);
-    stage_plane(S, x, qc, hal);
+    stage_plane<LEAN>(S, x, qc, hal);
     if constexpr (GUARD || DETECT) {
       if (GUARD || detect) stage_plane_flag(S, x, qc, hal, k0 & 1);
     }
     __syncthreads();
     bool flagged = false;
-    plane_sweeps<RIEMANN, RECON, false, CURV, GUARD, DETECT>(S, P, x, gx, k0, qc, false, qc, hal, fx_lo, fy_lo, flagged, detect FPROF_PASS);
+    plane_sweeps<RIEMANN, RECON, false, CURV, GUARD, DETECT, LEAN>(S, P, x, gx, k0, qc, false, qc, hal, fx_lo, fy_lo, flagged, detect FPROF_PASS);
     if constexpr (CURV) {
       DFlux24 df{};
       if (gx.m3) gx.co.c3 = gx.m3[MT3_COS * (P.nk + 1) + k0], gx.co.s3 = gx.m3[MT3_SIN * (P.nk + 1) + k0];
@@ -939,8 +1008,8 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
       plane_update_curv<HAS_U1, WITH_DT, false>(S, P, a, src.v, x, gx, k0, qc, fx_lo, fy_lo, fz, fz, u1raw, df, ldt);
     }
     else if constexpr (FLUXES) plane_store_fluxes<false>(S, P, x, k0, fx_lo, fy_lo, fz, fz);
-    else plane_update<HAS_U1, WRITE_CONS, WITH_DT, false>(S, P, a, x, k0, qc, fx_lo, fy_lo, fz, fz, u1raw, ldt,
-                                                          flagged, shell_wg);
+    else plane_update<HAS_U1, WRITE_CONS, WITH_DT, false, LEAN>(S, P, a, x, k0, qc, fx_lo, fy_lo, fz, fz, u1raw, ldt,
+                                                                flagged, shell_wg);
   } else {
     // x3 state carried in registers: planes k, k+1, the upper face value of cell k and the
     // flux through face k.
@@ -976,11 +1045,13 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
         bool flat_ = false;
         if constexpr (SK6) {
 #define ZF0(m, n) &&plm_flat(qmm.m, qc.m, qn.m)
-          flat_ = f0 && __all(true FOR6(ZF0));
+          flat_ = f0 && __all(true FOR5(ZF0) && (LEAN || (true ZF0(e, 5))));
 #undef ZF0
         }
 #define ZL0(m, n) zl.m = up_val<RECON>(qc.m, flat_ ? 0.0 : slope_sel<RECON, SK1>(qmm.m, qc.m, qn.m, f0));
-        FOR6(ZL0)
+        FOR5(ZL0)
+        if constexpr (LEAN) zl.e = 0.0;
+        else { ZL0(e, 5) }
 #undef ZL0
       }
     }
@@ -1008,9 +1079,9 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
       Flux8 fx_lo, fy_lo;
       bool flagged = false;
       if (k >= k0) {
-        plane_sweeps<RIEMANN, RECON, true, CURV, GUARD, DETECT>(S, P, x, gx, k, qc, k < k1, qn, hal, fx_lo, fy_lo, flagged, detect FPROF_PASS);
+        plane_sweeps<RIEMANN, RECON, true, CURV, GUARD, DETECT, LEAN>(S, P, x, gx, k, qc, k < k1, qn, hal, fx_lo, fy_lo, flagged, detect FPROF_PASS);
       } else { // priming trip: stage the first plane
-        stage_plane(S, x, qn, hal);
+        stage_plane<LEAN>(S, x, qn, hal);
         if constexpr (GUARD || DETECT) {
           if (GUARD || detect) stage_plane_flag(S, x, qn, hal, k0 & 1);
         }
@@ -1056,10 +1127,11 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
     zr.m = lo_val<RECON>(qn.m, s_);                                                        \
     zl_next.m = up_val<RECON>(qn.m, s_);                                                   \
   }
-#define ZSL6(F) ZSL(d, F) ZSL(v1, F) ZSL(v2, F) ZSL(v3, F) ZSL(p, F) ZSL(e, F)
+#define ZSL6(F) ZSL(d, F) ZSL(v1, F) ZSL(v2, F) ZSL(v3, F) ZSL(p, F) if constexpr (!LEAN) ZSL(e, F)
+        if constexpr (LEAN) zr.e = zl_next.e = 0.0;
         if constexpr (SK6) {
 #define ZF(m, n) &&plm_flat(qc.m, qn.m, qnn.m)
-          if (fast_col && __all(true FOR6(ZF))) { ZSL6(true) } else { ZSL6(false) }
+          if (fast_col && __all(true FOR5(ZF) && (LEAN || (true ZF(e, 5))))) { ZSL6(true) } else { ZSL6(false) }
 #undef ZF
         } else {
           ZSL6(false)
@@ -1073,8 +1145,8 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
       if (k >= k0) {
         if constexpr (CURV) plane_update_curv<HAS_U1, WITH_DT, true>(S, P, a, src.v, x, gx, k, qc, fx_lo, fy_lo, fz_lo, fz_hi, u1raw, df, ldt);
         else if constexpr (FLUXES) plane_store_fluxes<true>(S, P, x, k, fx_lo, fy_lo, fz_lo, fz_hi);
-        else plane_update<HAS_U1, WRITE_CONS, WITH_DT, true>(S, P, a, x, k, qc, fx_lo, fy_lo, fz_lo, fz_hi, u1raw, ldt,
-                                                             flagged || (fhist & 3u) != 0u || ahead, shell_wg);
+        else plane_update<HAS_U1, WRITE_CONS, WITH_DT, true, LEAN>(S, P, a, x, k, qc, fx_lo, fy_lo, fz_lo, fz_hi, u1raw, ldt,
+                                                                   flagged || (fhist & 3u) != 0u || ahead, shell_wg);
       }
       FPROF(7);
       fz_lo = fz_hi, zl = zl_next, qc = qn, qn = qnn;
@@ -1106,6 +1178,12 @@ __global__ __launch_bounds__(NT, (CURV && !ARTEMIS_CURV_OCC2) ? 1 : 2) void stag
     }
   }
 }
+
+#undef STAGE_KERNEL_HEAD
+#undef STAGE_KERNEL_FLAGS
+#ifndef ARTEMIS_FUSED_LEAN_PASS
+#define ARTEMIS_FUSED_LEAN_PASS
+#include "kernels_fused.hip" // the kernel's text once more (inside the namespaces): stage_fused_kernel_lean
 
 // Comm-stream side of the shell-first hand-off: one wave polls the counter (relaxed, agent
 // scope, with s_sleep) until `target` workgroups have published, then acquires.  Kernels queued
@@ -1146,10 +1224,16 @@ struct RedoK {
   unsigned cap;
   const unsigned long long *list;
   int has_u1;
+  int total; // the cumulative count this list adds to: 0 = bulk (and whole launches), 1 = boundary shell
 };
+// Zones the redo kernel has recomputed on this device since the last reset (artemis_hip_redo_totals): what the deferrals
+// of a run amount to -- vanishing velocities, and the zones of the lean form that need the internal-energy equation.
+// [1]: the lists of shell workgroups (shell-first launches) and of region-1 launches; [0]: every other list.
+__device__ unsigned long long g_redo_total[2];
 template <int RIEMANN, int RECON>
 __global__ __launch_bounds__(256) void stage_redo_kernel(const PackView P, const RedoK a) {
   const unsigned n = min(__hip_atomic_load(a.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a.cap);
+  if (n != 0u && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_redo_total[a.total], static_cast<unsigned long long>(n));
   const GasK gk = gas_constants(P.gm1);
   const FluidView &f = P.gas;
   const unsigned long long N = static_cast<unsigned long long>(P.nk) * P.nj * P.ni;
@@ -1310,12 +1394,15 @@ int pick_chunk(int planes, long tiles, long slots, int cmax = 16) {
 }
 
 template <int RIEMANN, int RECON>
-int launch_cfg(const PackView &P, const StageK &k, bool has_u1, bool cons, bool dt, hipStream_t s) {
+int launch_cfg(const PackView &P, const StageK &k, bool has_u1, bool cons, bool dt, bool lean, hipStream_t s) {
   const dim3 grid(k.start[k.nbox]);
   const dim3 block(FTX, FTY);
 #define GO(U, C, D)                                                                        \
   do {                                                                                     \
-    if (P.ndim > 2) hipLaunchKernelGGL((stage_fused_kernel<RIEMANN, RECON, U, C, D, true>), grid, block, 0, s, P, k, SrcArg<false>{}); \
+    if (lean) {                                                                            \
+      if (P.ndim > 2) hipLaunchKernelGGL((stage_fused_kernel_lean<RIEMANN, RECON, U, C, D, true>), grid, block, 0, s, P, k, SrcArg<false>{}); \
+      else hipLaunchKernelGGL((stage_fused_kernel_lean<RIEMANN, RECON, U, C, D, false>), grid, block, 0, s, P, k, SrcArg<false>{}); \
+    } else if (P.ndim > 2) hipLaunchKernelGGL((stage_fused_kernel<RIEMANN, RECON, U, C, D, true>), grid, block, 0, s, P, k, SrcArg<false>{}); \
     else hipLaunchKernelGGL((stage_fused_kernel<RIEMANN, RECON, U, C, D, false>), grid, block, 0, s, P, k, SrcArg<false>{}); \
   } while (0)
   if (has_u1) {
@@ -1425,7 +1512,8 @@ void launch_redo(const PackView &P, const artemis_stage_args_t &a, int riemann, 
   r.cnt = B.cnt + which, r.done = B.cnt + 2 + which, r.cap = static_cast<unsigned>(std::min<size_t>(B.cap, 0xffffffffu));
   r.list = B.list[which];
   r.has_u1 = (a.prim_u1 != a.prim_in) ? 1 : 0;
-#define RC(RS)                                                                             \
+  r.total = (which == 1 || a.region == 1) ? 1 : 0; // a region-1 launch is the boundary shell of the two-launch overlap
+#define RC(RS)                                                                            \
   case RS:                                                                                 \
     if (recon == ARTEMIS_PCM) launch_redo_cfg<RS, 0>(P, r, s);                             \
     else launch_redo_cfg<RS, 1>(P, r, s);                                                  \
@@ -1546,11 +1634,15 @@ int launch_stage_fused(const PackView &P, const artemis_stage_args_t &a, int rie
   const bool has_u1 = (a.prim_u1 != a.prim_in);
   const bool cons = (a.cons_out != nullptr);
   const bool dt = (a.dt_dev != nullptr);
+  // The lean form (no internal-energy equation; the zones that need it go to the redo list) where that list is short:
+  // with gas/de_switch = 0 the equation serves only zones whose total-energy update left no positive internal energy.
+  // A positive switch may defer a large share of the zones to the 32-workgroup redo kernel: the full form.
+  const bool lean = redo && !opt(OPT_NO_LEAN_ENERGY) && (P.gas.de_switch == 0.0 || opt(OPT_LEAN_ENERGY));
   int rc = 4;
 #define RC(RS)                                                                             \
   case RS:                                                                                 \
-    rc = (recon == ARTEMIS_PCM) ? launch_cfg<RS, 0>(P, k, has_u1, cons, dt, s)             \
-                                : launch_cfg<RS, 1>(P, k, has_u1, cons, dt, s);            \
+    rc = (recon == ARTEMIS_PCM) ? launch_cfg<RS, 0>(P, k, has_u1, cons, dt, lean, s)       \
+                                : launch_cfg<RS, 1>(P, k, has_u1, cons, dt, lean, s);      \
     break;
   switch (riemann) {
     RC(0)
@@ -1683,6 +1775,18 @@ void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args
 #undef RC
 }
 
+// The redo kernel's cumulative zone counts of the current device ([0] bulk lists, [1] shell lists), after everything
+// queued on it has finished; reset != 0 zeroes them.
+int redo_totals(unsigned long long *out, int reset) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_redo_total), 2 * sizeof(unsigned long long)) != hipSuccess) return 1;
+  if (reset) {
+    const unsigned long long z[2] = {0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_redo_total), z, sizeof z) != hipSuccess) return 1;
+  }
+  return 0;
+}
+
 #ifdef FUSED_PROF
 extern "C" int artemis_hip_debug_fused_prof(unsigned long long *out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fused_prof), sizeof(unsigned long long) * 16) != hipSuccess) return 1;
@@ -1694,3 +1798,4 @@ extern "C" int artemis_hip_debug_fused_prof(unsigned long long *out, int reset) 
 }
 #endif
 } // namespace artemis
+#endif // ARTEMIS_FUSED_LEAN_PASS (the tail: first pass only)

@@ -12,6 +12,8 @@ namespace artemis {
   X(NO_TUNED) X(TUNED_2D) X(NO_STAGE2D) X(NO_FUSED_CURV) X(NO_CURV_MARCH) X(NO_CURV_DUST) X(NO_CURV_DUST_MARCH) X(NO_DRAG_IN_MARCH) X(NO_STRAT_IN_KERNEL) X(NO_CART_MARCH) X(NO_CART_DUST_MARCH) X(NO_PPM_MARCH) X(NO_IC_IN_SHELL) X(NO_IC_SKIP) \
   X(NO_ML_FUSED) X(NO_EPILOGUE) X(NO_TILED_FLUX) X(NO_VISC_SOURCE) X(NBODY_TASK) X(NBODY_GENERAL)    \
   X(NO_PLM_TABLE) X(NO_DISTANCE_TABLE) X(NO_FLAT_RANGES) X(FULL_REMESH)                              \
+  X(NO_LEAN_ENERGY) /* the Cartesian stage always carries the internal-energy equation (the full kernel) */ \
+  X(LEAN_ENERGY) /* ... leaves it to the redo list whatever gas/de_switch is, while redo is on (tests) */ \
   /* exactness machinery (measuring what it costs) */                                                \
   X(NO_REDO) X(NO_TINY_HINT) X(NO_ML_FLOOR)                                                                   \
   /* host loop */                                                                                    \

@@ -52,7 +52,9 @@
  *    NO_EPILOGUE, NO_TILED_FLUX, NO_VISC_SOURCE (the diffusion-flux tasks instead of artemis_hip_viscous_source),
  *    NBODY_TASK (N-body gravity as its own task with the host-side reduction), NBODY_GENERAL, NO_PLM_TABLE,
  *    NO_DISTANCE_TABLE, NO_FLAT_RANGES, FULL_REMESH (a remesh rebuilds the whole state next to the old one instead of
- *    the lean hand-over)
+ *    the lean hand-over), NO_LEAN_ENERGY (artemis_hip_stage_fused always runs the kernel that carries the internal-energy
+ *    equation; default: with the redo list on and gas/de_switch = 0 the lean kernel, which defers the zones that need that
+ *    equation to the list), LEAN_ENERGY (the lean kernel for any gas/de_switch while the redo list is on: tests)
  *  exactness machinery
  *    NO_REDO         artemis_hip_stage_fused / the 2-D row march: switches off the detect-and-redo of zones next to
  *                    vanishing velocities (the hand-scheduled divisions are then NOT exact there: DESIGN.md section 4
@@ -479,6 +481,9 @@ typedef struct artemis_stage_args {
 size_t artemis_hip_redo_scratch_bytes(const artemis_pack_t *p);
 int artemis_hip_stage_fused(const artemis_pack_t *p, const artemis_stage_args_t *a, void *stream);
 int artemis_hip_stage_fused_redo_shell(const artemis_pack_t *p, const artemis_stage_args_t *a, void *stream);
+/* Zones the list-driven kernel has recomputed on the current device since the last reset: totals[0] from the lists of
+ * whole launches and bulk workgroups, totals[1] from shell lists.  Waits for the device; reset != 0 zeroes both. */
+int artemis_hip_redo_totals(unsigned long long totals[2], int reset);
 /* ---- gas diffusion (viscosity, heat conduction) ------------------------------------------
  * Gas::ZeroDiffusionFlux / ViscousFlux<GEOM> / ThermalFlux<GEOM> / DiffusionUpdate<GEOM>
  * (gas.cpp:522-641 -> utils/diffusion/{diffusion,momentum_diffusion,thermal_diffusion}.hpp),

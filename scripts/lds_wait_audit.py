@@ -18,6 +18,7 @@ Definitions (text order of the assembly; control flow inside the region is ignor
              wait: nothing of the wave's own covers the round trip.
 The count is static: one per instruction in the text, whatever share of the waves runs the branch it stands in.
 """
+import functools
 import os
 import re
 import subprocess
@@ -130,7 +131,13 @@ def demangle(names):
 
 
 def table(source, extra=()):
-    """[(demangled kernel name, audit counts + resource fields)] for every kernel of the source."""
+    """[(demangled kernel name, audit counts + resource fields)] for every kernel of the source (compiled once per
+    process and command line: two test modules ask for the same table)."""
+    return list(_table(source, tuple(extra)))
+
+
+@functools.lru_cache(maxsize=None)
+def _table(source, extra):
     ks = kernels(compile_asm(source, extra))
     rows = []
     for name, short in zip(ks, demangle(ks)):

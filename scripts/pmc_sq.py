@@ -52,9 +52,10 @@ res = {k[:150]: v for k, v in acc.items()}
 json.dump(res, open(os.path.join(OUT, "sq_%s.json" % tag), "w"), indent=1)
 if os.environ.get("PMC_SQ_RECORD"):
     # the record bench.py quotes as roofline.fp64_issue (only while the kernel sources are unchanged): mean VALU
-    # wave-instructions per launch over the headline stage kernels (non-curvilinear, non-flux instantiations)
+    # wave-instructions per launch over the headline stage kernels (non-curvilinear, non-flux instantiations; the lean
+    # form, stage_fused_kernel_lean<...>, is what the headline launches with gas/de_switch = 0)
     sys.path.insert(0, ROOT)
-    ks = {k: v for k, v in res.items() if "stage_fused_kernel" in k and "SQ_INSTS_VALU" in v}
+    ks = {k: v for k, v in res.items() if ("stage_fused_kernel<" in k or "stage_fused_kernel_lean<" in k) and "SQ_INSTS_VALU" in v}
     if ks:
         rec = {"library_identity": library_identity("fused"), "command": " ".join(prog), "env": {},
                "valu_wave_instructions_per_launch": sum(v["SQ_INSTS_VALU"] for v in ks.values()) / len(ks),

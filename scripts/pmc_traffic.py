@@ -24,6 +24,7 @@ import csv
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -201,8 +202,8 @@ def main():
     # the dropin and emulation legs.  (A run with them also launches the WRITE_CONS instantiations -- 4th template
     # argument true -- and the FLUXES one -- 8th true: the flux TASK through the tile march; off_headline guards
     # against those should the flags change.)
-    def off_headline(name):
-        targs = [t.strip() for t in name.split("stage_fused_kernel<", 1)[1].split(">", 1)[0].split(",")]
+    def off_headline(name):  # (either form of the kernel: stage_fused_kernel<...> or stage_fused_kernel_lean<...>)
+        targs = [t.strip() for t in re.split(r"stage_fused_kernel(?:_lean)?<", name, 1)[1].split(">", 1)[0].split(",")]
         return targs[3] == "true" or (len(targs) > 7 and targs[7] == "true")
     for k2, v in stage.items():
         v["headline_path"] = not off_headline(k2)
