@@ -34,6 +34,11 @@ DRAG_SIMPLE_DUST, DRAG_SELF = 1, 2
 DRAG_CONSTANT, DRAG_STOKES = 0, 1
 DIFF_OFF, VISCOSITY_PLAW, VISCOSITY_ALPHA, CONDUCTIVITY_PLAW, THERMALDIFF_PLAW = range(5)
 MAX_DUST_SPECIES = 16
+# enum artemis_field_var: the variables of artemis_hip_pack_fields, by the names an output block's `variables` line uses
+FIELD_VARS = ("gas.prim.density", "gas.prim.velocity", "gas.prim.pressure", "gas.prim.sie", "gas.cons.density",
+              "gas.cons.momentum", "gas.cons.total_energy", "gas.cons.internal_energy", "dust.prim.density",
+              "dust.prim.velocity", "dust.cons.density", "dust.cons.momentum")
+FIELD_VAR = {name: code for code, name in enumerate(FIELD_VARS)}
 RSOLVER = {"hllc": HLLC, "hlle": HLLE, "llf": LLF}
 RECON = {"pcm": PCM, "plm": PLM, "ppm": PPM}
 BCS = {"periodic": BC_PERIODIC, "outflow": BC_OUTFLOW, "reflecting": BC_REFLECT,
@@ -211,6 +216,8 @@ def load():
         "artemis_hip_estimate_dt_async": (i, [PPk, i, d, vp, vp]),
         "artemis_hip_history_scratch_bytes": (C.c_size_t, [PPk]),
         "artemis_hip_history_sums": (i, [PPk, vp, vp, vp]),
+        "artemis_hip_pack_fields_bytes": (C.c_size_t, [PPk, i, C.POINTER(i), i]),
+        "artemis_hip_pack_fields": (i, [PPk, i, i, i, C.POINTER(i), i, vp, vp]),
         "artemis_hip_apply_bc": (i, [PPk, C.POINTER(i), C.POINTER(BcParams), vp]),
         "artemis_hip_external_gravity": (i, [PPk, C.POINTER(Gravity), d, d, vp]),
         "artemis_hip_rotating_frame_force": (i, [PPk, d, d, d, d, vp]),
@@ -311,7 +318,7 @@ EXPORTS_HIP = [
     "artemis_hip_calculate_fluxes", "artemis_hip_apply_update", "artemis_hip_flux_source",
     "artemis_hip_set_aux", "artemis_hip_cons_to_prim", "artemis_hip_prim_to_cons", "artemis_hip_prim_to_cons_ghosts",
     "artemis_hip_deep_copy_conserved", "artemis_hip_estimate_dt", "artemis_hip_estimate_dt_async",
-    "artemis_hip_history_scratch_bytes", "artemis_hip_history_sums",
+    "artemis_hip_history_scratch_bytes", "artemis_hip_history_sums", "artemis_hip_pack_fields_bytes", "artemis_hip_pack_fields",
     "artemis_hip_apply_bc", "artemis_hip_stage_fused", "artemis_hip_stage_fused_redo_shell", "artemis_hip_redo_totals", "artemis_hip_metric_count",
     "artemis_hip_metric_fill", "artemis_hip_external_gravity", "artemis_hip_nbody_gravity", "artemis_hip_nbody_force_scratch",
     "artemis_hip_nbody_force_sums", "artemis_hip_timestep_all", "artemis_hip_redo_scratch_bytes", "artemis_hip_rotating_frame_force",

@@ -253,6 +253,46 @@ int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_dev, double *
   return after_launch("history_sums");
 }
 
+// the selection of artemis_hip_pack_fields as the kernel takes it; "" or what is wrong with it
+static const char *field_selection(const artemis_pack_t *p, int nsel, const int *sel, artemis::FieldSelection &S) {
+  std::memset(&S, 0, sizeof S);
+  if (nsel < 0 || nsel > artemis::FIELDS_MAX_SEL || (nsel > 0 && !sel)) return "pack fields: 0 to 32 variable codes are taken";
+  for (int e = 0; e < nsel; ++e) {
+    const int code = sel[e];
+    if (code < 0 || code >= ARTEMIS_VAR_COUNT) return "pack fields: unknown variable code";
+    const bool dust = code >= ARTEMIS_VAR_DUST_PRIM_DENSITY;
+    const int ns = dust ? p->dust.nspecies : p->gas.nspecies;
+    if (ns < 1) return dust ? "pack fields: a dust variable on a pack without dust" : "pack fields: a gas variable on a pack without gas";
+    const bool vec = code == ARTEMIS_VAR_GAS_PRIM_VELOCITY || code == ARTEMIS_VAR_GAS_CONS_MOMENTUM ||
+                     code == ARTEMIS_VAR_DUST_PRIM_VELOCITY || code == ARTEMIS_VAR_DUST_CONS_MOMENTUM;
+    S.code[e] = code, S.comp0[e] = S.ncomp, S.ncomp += (vec ? 3 : 1) * ns;
+    (dust ? S.want_dust : S.want_gas) = 1;
+  }
+  S.nsel = nsel;
+  return "";
+}
+size_t artemis_hip_pack_fields_bytes(const artemis_pack_t *p, int nsel, const int *sel, int single) {
+  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return 0;
+  artemis::FieldSelection S;
+  if (*field_selection(p, nsel, sel, S)) return 0;
+  return static_cast<size_t>(p->nblocks) * S.ncomp * p->nx1 * p->nx2 * p->nx3 * (single ? sizeof(float) : sizeof(double));
+}
+int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, void *out_dev,
+                            void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldSelection F;
+  const char *bad = field_selection(p, nsel, sel, F);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
+    return fail(ARTEMIS_HIP_EINVAL, "pack fields: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
+  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "pack fields: the primitive tables of the fluids asked for are required");
+  if (nblocks == 0 || F.ncomp == 0) return 0;
+  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "pack fields: null out_dev");
+  artemis::launch_pack_fields(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, out_dev, S(stream));
+  return after_launch("pack_fields");
+}
+
 int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, double *dt_out,
                             void *stream) {
   if (!dt_out) return fail(ARTEMIS_HIP_EINVAL, "null dt_out");

@@ -38,6 +38,10 @@
 extern "C" size_t artemis_hip_history_scratch_bytes(const artemis_pack_t *p) __attribute__((weak));
 extern "C" int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_dev, double *scratch_dev, void *stream)
     __attribute__((weak));
+// ... and so is the kernel of the field outputs: without it the gather forms the same expressions in a host loop
+extern "C" int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                       void *out_dev, void *stream) __attribute__((weak));
+static_assert(artemis_out::kFieldVars == ARTEMIS_VAR_COUNT, "outputs_hooks.hpp names every artemis_field_var");
 
 #define SQR(x) ((x) * (x))
 typedef double Real;
@@ -486,6 +490,10 @@ struct artemis_sim_impl {
   int history(double *out);
   DevBuf hist_sums, hist_scratch; // artemis_hip_history_sums: its result and its rows of partial sums, sized for this pack
   int history_device(double *out);
+  // artemis_sim_gather_fields: the device staging buffer of artemis_hip_pack_fields -- a whole number of blocks and at
+  // most FIELDS_STAGE_MB (default 256) MiB, one block where a block is larger; allocated by the first gather
+  DevBuf field_stage;
+  size_t gather_fields(const std::vector<int> &codes, bool single, void *host_out);
   int errors(double *out);
 };
 
@@ -3495,6 +3503,111 @@ int artemis_sim_impl::history_device(double *out) {
   return nout;
 }
 
+// Field output: the variables `codes` (enum artemis_field_var) of this rank's interior zones as [block][component][nk][nj]
+// [ni], double or float, formed from the primitives of the current buffer with PrimToCons's expressions: by
+// artemis_hip_pack_fields into a bounded staging buffer, one copy per block range (kernels_fields.hip), or -- a library
+// without that kernel -- in a host loop over the downloaded primitives.  Nothing is materialised: cons_valid stays as it is.
+size_t artemis_sim_impl::gather_fields(const std::vector<int> &codes, bool single, void *host_out) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  std::vector<int> comp0;
+  int ncomp = 0;
+  for (const int code : codes) {
+    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
+    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
+    comp0.push_back(ncomp), ncomp += n;
+  }
+  const size_t zones = static_cast<size_t>(mbnx[0]) * mbnx[1] * mbnx[2], esz = single ? sizeof(float) : sizeof(double);
+  const size_t block_bytes = static_cast<size_t>(ncomp) * zones * esz;
+  if (!host_out || block_bytes == 0) return static_cast<size_t>(nb) * block_bytes;
+  if (artemis_hip_pack_fields) {
+    const artemis_pack_t p = make_pack(base);
+    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
+    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
+    const int per = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(nb), cap / block_bytes)));
+    const size_t need = (static_cast<size_t>(per) * block_bytes + sizeof(double) - 1) / sizeof(double);
+    if (field_stage.n < need) field_stage.alloc(need);
+    for (int b0 = 0; b0 < nb; b0 += per) {
+      const int n = std::min(per, nb - b0);
+      CK(artemis_hip_pack_fields(&p, b0, n, static_cast<int>(codes.size()), codes.data(), single ? 1 : 0, field_stage.p, stream), "pack fields");
+      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(b0) * block_bytes, field_stage.p,
+                               static_cast<size_t>(n) * block_bytes, stream), "d2h");
+      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffer)
+    }
+    return static_cast<size_t>(nb) * block_bytes;
+  }
+  for (int b = 0; b < nb; ++b) {
+    std::vector<Real> g, d;
+    if (nsg) g = download(gprim[base], b);
+    if (nsd) d = download(dprim[base], b);
+    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(b) * block_bytes;
+    for (int k = ks; k <= ke; ++k)
+      for (int j = js; j <= je; ++j)
+        for (int i = is; i <= ie; ++i) {
+          const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
+          const size_t z = (static_cast<size_t>(k - ks) * mbnx[1] + (j - js)) * mbnx[0] + (i - is);
+          auto put = [&](int comp, Real v) {
+            if (single) reinterpret_cast<float *>(ob)[comp * zones + z] = static_cast<float>(v);
+            else reinterpret_cast<double *>(ob)[comp * zones + z] = v;
+          };
+          Real hx[3] = {1.0, 1.0, 1.0}; // GetScaleFactors (geometry.hpp:384-388)
+          if (coords != ARTEMIS_CARTESIAN) {
+            const artemis::DCoords co = cell_coords(b, k, j, i);
+            hx[1] = co.hx2v(), hx[2] = co.hx3v();
+          }
+          for (int n = 0; n < nsg; ++n) { // prim_to_cons_kernel's expressions (kernels_unfused.hip; fill_derived.cpp:212-276)
+            Real w_d = g[n * N + c];
+            w_d = (w_d > dfloor_gas) ? w_d : dfloor_gas;
+            const Real vel[3] = {g[(nsg + 3 * n + 0) * N + c], g[(nsg + 3 * n + 1) * N + c], g[(nsg + 3 * n + 2) * N + c]};
+            Real w_s = g[(5 * nsg + n) * N + c];
+            w_s = (w_s > siefloor_gas) ? w_s : siefloor_gas;
+            const Real u_u = w_s * w_d;
+            const Real ke = 0.5 * w_d * (SQR(vel[0]) + SQR(vel[1]) + SQR(vel[2]));
+            for (size_t e = 0; e < codes.size(); ++e) {
+              const int at = comp0[e];
+              switch (codes[e]) {
+              case ARTEMIS_VAR_GAS_PRIM_DENSITY:
+              case ARTEMIS_VAR_GAS_CONS_DENSITY: put(at + n, w_d); break;
+              case ARTEMIS_VAR_GAS_PRIM_VELOCITY:
+                for (int q = 0; q < 3; ++q) put(at + 3 * n + q, vel[q]);
+                break;
+              case ARTEMIS_VAR_GAS_PRIM_PRESSURE: {
+                const Real pr = (gamma - 1.0) * w_d * w_s;
+                put(at + n, (0.0 < pr) ? pr : 0.0);
+              } break;
+              case ARTEMIS_VAR_GAS_PRIM_SIE: put(at + n, w_s); break;
+              case ARTEMIS_VAR_GAS_CONS_MOMENTUM:
+                for (int q = 0; q < 3; ++q) put(at + 3 * n + q, w_d * vel[q] * hx[q]);
+                break;
+              case ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY: put(at + n, u_u + ke); break;
+              case ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY: put(at + n, u_u); break;
+              default: break;
+              }
+            }
+          }
+          for (int m = 0; m < nsd; ++m) {
+            Real w_d = d[m * N + c];
+            w_d = (w_d > dfloor_dust) ? w_d : dfloor_dust;
+            const Real vel[3] = {d[(nsd + 3 * m + 0) * N + c], d[(nsd + 3 * m + 1) * N + c], d[(nsd + 3 * m + 2) * N + c]};
+            for (size_t e = 0; e < codes.size(); ++e) {
+              const int at = comp0[e];
+              switch (codes[e]) {
+              case ARTEMIS_VAR_DUST_PRIM_DENSITY:
+              case ARTEMIS_VAR_DUST_CONS_DENSITY: put(at + m, w_d); break;
+              case ARTEMIS_VAR_DUST_PRIM_VELOCITY:
+                for (int q = 0; q < 3; ++q) put(at + 3 * m + q, vel[q]);
+                break;
+              case ARTEMIS_VAR_DUST_CONS_MOMENTUM:
+                for (int q = 0; q < 3; ++q) put(at + 3 * m + q, w_d * vel[q] * hx[q]);
+                break;
+              default: break;
+              }
+            }
+          }
+        }
+  }
+  return static_cast<size_t>(nb) * block_bytes;
+}
+
 // linear_wave.hpp:267-377 / advection.hpp:224-405 UserWorkAfterLoop
 int artemis_sim_impl::errors(double *out) {
   if (pgen != PG_LINWAVE && pgen != PG_ADVECTION) return 0;
@@ -3935,6 +4048,34 @@ const std::vector<std::string> &overrides_of(const artemis_sim_t *sim) { return 
 State *&state_of(artemis_sim_t *sim) { return sim->outputs; }
 const State *state_of(const artemis_sim_t *sim) { return sim->outputs; }
 int history_sums(artemis_sim_t *sim, double *out) { return sim->p->history_device(out); }
+size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out) {
+  return sim->p->gather_fields(codes, single, host_out);
+}
+FieldsLayout fields_layout(artemis_sim_t *sim) {
+  const artemis_sim_impl &S = *sim->p;
+  static const char *const names[6] = {"cartesian", "cylindrical", "spherical1D", "spherical2D", "spherical3D", "axisymmetric"};
+  FieldsLayout L;
+  L.coordinates = names[S.coords], L.ndim = S.ndim, L.rank = S.rank, L.nranks = S.nranks, L.gamma = S.gamma;
+  for (int d = 0; d < 3; ++d) L.nx[d] = S.mbnx[d];
+  // rows {level, rank, index, bounds[6]} by gid: every rank fills its own, the sum over the ranks adds zeros to them
+  const int row = 9;
+  std::vector<double> t(static_cast<size_t>(S.nblocks_global) * row, 0.0);
+  for (int b = 0; b < S.nb; ++b) {
+    double *r = t.data() + static_cast<size_t>(S.blocks[b].gid) * row;
+    r[0] = S.blocks[b].level, r[1] = S.rank, r[2] = b;
+    for (int d = 0; d < 3; ++d) r[3 + 2 * d] = S.blocks[b].xmin[d], r[4 + 2 * d] = S.blocks[b].xmax[d];
+  }
+  if (S.has_comm && S.nranks > 1 && S.comm.allreduce_sum(S.comm.ctx, t.data(), static_cast<int>(t.size())))
+    throw std::runtime_error("allreduce failed");
+  L.blocks.resize(static_cast<size_t>(S.nblocks_global));
+  for (long g = 0; g < S.nblocks_global; ++g) {
+    const double *r = t.data() + static_cast<size_t>(g) * row;
+    FieldBlock &B = L.blocks[static_cast<size_t>(g)];
+    B.gid = g, B.level = static_cast<int>(r[0]), B.rank = static_cast<int>(r[1]), B.index = static_cast<int>(r[2]);
+    for (int q = 0; q < 6; ++q) B.bounds[q] = r[3 + q];
+  }
+  return L;
+}
 
 } // namespace artemis_out
 
@@ -4191,6 +4332,30 @@ int artemis_sim_history_device(artemis_sim_t *s, double *out) {
   }
   GUARD(n = s->p->history_device(out), return -1)
   return n;
+}
+long artemis_sim_gather_fields(artemis_sim_t *s, int nvar, const char *const *names, int single, void *host_out) {
+  long ret = -1;
+  if (!s->dead.empty()) {
+    g_sim_err = s->dead;
+    return -1;
+  }
+  auto gather = [&]() {
+    const artemis_out::Clock c = artemis_out::clock_of(s);
+    std::vector<int> codes;
+    int ncomp = 0;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = artemis_out::field_var_code(name);
+      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
+      if (n == 0) throw std::runtime_error("gather_fields: unknown variable " + name);
+      codes.push_back(code);
+      ncomp += n;
+    }
+    const size_t bytes = s->p->gather_fields(codes, single != 0, host_out);
+    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
+  };
+  GUARD(gather(), return -1)
+  return ret;
 }
 int artemis_sim_errors(artemis_sim_t *s, double *out) {
   int n = -1;

@@ -1,6 +1,7 @@
 // Deck-driven periodic outputs of the host driver (include/artemis_driver.h: artemis_sim_enable_outputs /
 // _outputs_describe): the scheduler of the deck's <parthenon/outputN> blocks and the writer of history files.  Plain C++
-// like the rest of the driver; the state is reached through outputs_hooks.hpp, dumps go through artemis_sim_save.
+// like the rest of the driver; the state is reached through outputs_hooks.hpp, dumps go through artemis_sim_save, field
+// dumps (`fld`: a directory of meta.json + one raw part per rank, artemis_sim_write_fields) are written here.
 //
 // Schedule (parthenon's Outputs::MakeOutputs, upstream): a block is due when time >= next_time; after it has been
 // written next_time is the smallest m * dt, m an integer, above time -- by multiplication, so the times do not drift.  A
@@ -8,6 +9,7 @@
 // An output time is never passed to the time step.
 #include <algorithm>
 #include <cerrno>
+#include <dirent.h>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +18,7 @@
 #include <string>
 #include <sys/stat.h>
 #include <sys/types.h>
+#include <unistd.h>
 #include <vector>
 
 #include "artemis_driver.h"
@@ -26,7 +29,7 @@
 namespace artemis_out {
 
 namespace {
-enum Kind { HST, RST, SKIPPED };
+enum Kind { HST, RST, FLD, SKIPPED };
 
 struct OutBlock {
   std::string name, file_type; // "parthenon/output0", "hst"
@@ -36,7 +39,12 @@ struct OutBlock {
   long written = 0, last_cycle = -1, last_final_cycle = -1;
   long counter = 0;          // rst: number of the next dump
   bool header_done = false;  // hst: this run has written its header section
-  std::string path;          // hst: the file; rst: the last dump
+  std::string path;          // hst: the file; rst, fld: the last dump
+  // fld: the names of its `variables` list and their codes, single_precision_output; why the block is skipped, if it is
+  std::vector<std::string> variables;
+  std::vector<int> codes;
+  bool single = false, is_fld = false;
+  std::string skip;
 };
 
 // smallest m * dt (m an integer) strictly above t
@@ -85,6 +93,30 @@ struct State {
 
 namespace {
 
+// A `fld` block: its comma list of variables against the table of outputs_hooks.hpp and the species of the run
+void parse_fld(artemis_host::ParameterInput &pin, const Clock &c, OutBlock &b) {
+  b.is_fld = true, b.kind = FLD;
+  b.single = pin.GetOrAddBoolean(b.name, "single_precision_output", false);
+  std::string list = pin.DoesParameterExist(b.name, "variables") ? pin.GetString(b.name, "variables") : "";
+  for (size_t at = 0; at <= list.size();) {
+    size_t end = list.find(',', at);
+    if (end == std::string::npos) end = list.size();
+    std::string name = list.substr(at, end - at);
+    const size_t a = name.find_first_not_of(" \t"), z = name.find_last_not_of(" \t");
+    if (a != std::string::npos) b.variables.push_back(name.substr(a, z - a + 1));
+    at = end + 1;
+  }
+  if (b.variables.empty()) b.skip = "no variables";
+  for (const std::string &name : b.variables) {
+    const int code = field_var_code(name);
+    if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) {
+      if (b.skip.empty()) b.skip = "unknown variable " + name;
+    } else b.codes.push_back(code);
+  }
+  if (b.skip.empty() && pin.GetOrAddBoolean(b.name, "ghost_zones", false)) b.skip = "ghost_zones is not built";
+  if (!b.skip.empty()) b.kind = SKIPPED;
+}
+
 // The <parthenon/outputN> blocks of deck + overrides.  A block without a positive dt can never become due: skipped.
 std::unique_ptr<State> parse(const artemis_sim_t *sim) {
   artemis_host::ParameterInput pin;
@@ -101,6 +133,7 @@ std::unique_ptr<State> parse(const artemis_sim_t *sim) {
     b.file_type = pin.DoesParameterExist(name, "file_type") ? pin.GetString(name, "file_type") : "";
     b.dt = pin.DoesParameterExist(name, "dt") ? pin.GetReal(name, "dt") : 0.0;
     b.kind = (b.file_type == "hst") ? HST : ((b.file_type == "rst") ? RST : SKIPPED);
+    if (b.file_type == "fld") parse_fld(pin, clock_of(sim), b);
     st->blocks.push_back(b);
   }
   // (BlocksWithPrefix walks a sorted set: output10 would come before output2)
@@ -112,6 +145,7 @@ std::unique_ptr<State> parse(const artemis_sim_t *sim) {
 bool acted_on(const OutBlock &b) { return b.kind != SKIPPED && b.dt > 0.0 && std::isfinite(b.dt); }
 
 std::string status_of(const State &st, const OutBlock &b) {
+  if (b.kind == SKIPPED && !b.skip.empty()) return "skipped: " + b.skip;
   if (b.kind == SKIPPED) return "skipped: " + (b.file_type.empty() ? std::string("no file_type") : b.file_type + " is not built");
   if (!acted_on(b)) return "skipped: no positive dt";
   return st.on ? "active" : "inactive: outputs are not enabled";
@@ -164,6 +198,131 @@ void write_dump(artemis_sim_t *sim, State &st, OutBlock &b, bool final) {
   if (!final) b.counter++;
 }
 
+// `failed` summed over the ranks (barrier and vote in one); true if anybody failed
+bool vote(artemis_sim_t *sim, bool failed) {
+  const artemis_comm_t *comm = artemis_ckpt::comm_of(sim);
+  if (!comm || comm->nranks <= 1) return failed;
+  double v = failed ? 1.0 : 0.0;
+  if (!comm->allreduce_sum || comm->allreduce_sum(comm->ctx, &v, 1)) return true;
+  return v > 0.0;
+}
+
+// meta.json, the rank parts and the directory itself; anything else in there is not ours and keeps the directory
+void remove_field_dir(const std::string &dir) {
+  DIR *d = opendir(dir.c_str());
+  if (!d) {
+    if (errno == ENOENT) return;
+    throw std::runtime_error("cannot open " + dir + ": " + std::strerror(errno));
+  }
+  std::vector<std::string> names;
+  while (struct dirent *e = readdir(d)) {
+    const std::string n = e->d_name;
+    const bool part = n.size() > 8 && n.compare(0, 4, "rank") == 0 && n.compare(n.size() - 4, 4, ".bin") == 0 &&
+                      n.find_first_not_of("0123456789", 4) == n.size() - 4;
+    if (n == "meta.json" || part) names.push_back(n);
+  }
+  closedir(d);
+  for (const std::string &n : names) unlink((dir + "/" + n).c_str());
+  if (rmdir(dir.c_str()) != 0) throw std::runtime_error("cannot replace " + dir + " (it holds files that are not parts of a field dump): " + std::strerror(errno));
+}
+
+void write_file(const std::string &name, const void *data, size_t bytes) {
+  std::FILE *f = std::fopen(name.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot open " + name + ": " + std::strerror(errno));
+  const bool bad = bytes && std::fwrite(data, 1, bytes, f) != bytes;
+  if (std::fclose(f) != 0 || bad) throw std::runtime_error("writing " + name + " failed");
+}
+
+std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single) {
+  std::string j = "{\"format\": \"artemis_fld\", \"version\": 1, \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
+                  ", \"cycle\": " + std::to_string(c.ncycle) + ", \"coordinates\": " + json_str(L.coordinates) +
+                  ", \"ndim\": " + std::to_string(L.ndim) + ", \"nghost\": 0, \"dtype\": " + (single ? "\"<f4\"" : "\"<f8\"") +
+                  ", \"gamma\": " + json_num(L.gamma) + ", \"ns_gas\": " + std::to_string(c.ns_gas) + ", \"ns_dust\": " + std::to_string(c.ns_dust) +
+                  ", \"nranks\": " + std::to_string(L.nranks);
+  const std::string nx = "[" + std::to_string(L.nx[0]) + ", " + std::to_string(L.nx[1]) + ", " + std::to_string(L.nx[2]) + "]";
+  j += ", \"nx\": " + nx + ",\n \"variables\": [";
+  for (size_t v = 0; v < codes.size(); ++v) {
+    const int ns = field_var_is_dust(codes[v]) ? c.ns_dust : c.ns_gas;
+    const std::string name = field_var_name(codes[v]);
+    j += std::string(v ? ", " : "") + "{\"name\": " + json_str(name) + ", \"ncomp\": " + std::to_string(field_var_components(codes[v], c.ns_gas, c.ns_dust)) +
+         ", \"components\": [";
+    for (int n = 0; n < ns; ++n)
+      for (int d = 0; d < (field_var_is_vector(codes[v]) ? 3 : 1); ++d)
+        j += std::string(n || d ? ", " : "") + json_str(name + "_" + std::to_string(n) + (field_var_is_vector(codes[v]) ? "_x" + std::to_string(d + 1) : ""));
+    j += "]}";
+  }
+  j += "],\n \"blocks\": [";
+  for (size_t g = 0; g < L.blocks.size(); ++g) {
+    const FieldBlock &B = L.blocks[g];
+    j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
+    for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
+    j += "], \"nx\": " + nx + ", \"rank\": " + std::to_string(B.rank) + ", \"index\": " + std::to_string(B.index) + "}";
+  }
+  return j + "]}\n";
+}
+
+// One field dump (artemis_driver.h: artemis_sim_write_fields).  Every rank takes every vote, whatever happened to it
+// before: the votes are collective.
+void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single) {
+  std::string err, dir = path_in, tmp;
+  while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
+  tmp = dir + ".tmp";
+  const Clock c = clock_of(sim);
+  FieldsLayout L;
+  try {
+    const std::string dead = artemis_ckpt::dead_reason(sim);
+    if (!dead.empty()) throw std::runtime_error(dead);
+    if (codes.empty()) throw std::runtime_error("no variables");
+    L = fields_layout(sim);
+    if (c.rank == 0) {
+      remove_field_dir(tmp);
+      if (::mkdir(tmp.c_str(), 0777) != 0) throw std::runtime_error("cannot create " + tmp + ": " + std::strerror(errno));
+    }
+  } catch (const std::exception &e) {
+    err = e.what();
+  }
+  bool failed = vote(sim, !err.empty());
+  if (!failed) {
+    try {
+      std::vector<char> host(gather_fields(sim, codes, single, nullptr));
+      gather_fields(sim, codes, single, host.data());
+      write_file(tmp + "/rank" + std::to_string(c.rank) + ".bin", host.data(), host.size());
+    } catch (const std::exception &e) {
+      err = e.what();
+    }
+    failed = vote(sim, !err.empty());
+  }
+  if (!failed) {
+    try {
+      if (c.rank == 0) {
+        const std::string meta = meta_json(c, L, codes, single);
+        write_file(tmp + "/meta.json", meta.data(), meta.size()); // last: a directory with it has all its parts
+        remove_field_dir(dir);
+        if (std::rename(tmp.c_str(), dir.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + dir + ": " + std::strerror(errno));
+      }
+    } catch (const std::exception &e) {
+      err = e.what();
+    }
+    failed = vote(sim, !err.empty());
+  }
+  if (!failed) return;
+  if (c.rank == 0) {
+    try {
+      remove_field_dir(tmp);
+    } catch (const std::exception &) {
+    }
+  }
+  throw std::runtime_error("write_fields: " + dir + ": " + (err.empty() ? std::string("another rank failed") : err));
+}
+
+void write_field_dump(artemis_sim_t *sim, State &st, OutBlock &b, bool final) {
+  char num[16];
+  std::snprintf(num, sizeof num, "%05ld", b.counter);
+  b.path = st.dir + "/" + st.problem_id + ".out" + std::to_string(b.index) + "." + (final ? std::string("final") : std::string(num)) + ".fld";
+  write_fields(sim, b.path, b.codes, b.single);
+  if (!final) b.counter++;
+}
+
 } // namespace
 
 void destroy(State *st) { delete st; }
@@ -185,11 +344,12 @@ bool write_due(artemis_sim_t *sim, bool history_only) {
     if (!acted_on(b)) continue;
     const Clock c = clock_of(sim);
     if (c.time < b.next_time) continue;
-    if (b.kind == RST && history_only) {
+    if (b.kind != HST && history_only) {
       dump_due = true;
       continue;
     }
     if (b.kind == HST) write_history(sim, *st, b);
+    else if (b.kind == FLD) write_field_dump(sim, *st, b, false);
     else write_dump(sim, *st, b, false);
     b.written++, b.last_cycle = c.ncycle;
     b.next_time = next_multiple(c.time, b.dt);
@@ -209,7 +369,8 @@ void write_final(artemis_sim_t *sim) {
       b.written++, b.last_cycle = c.ncycle;
     } else {
       if (b.last_final_cycle == c.ncycle) continue;
-      write_dump(sim, *st, b, true);
+      if (b.kind == FLD) write_field_dump(sim, *st, b, true);
+      else write_dump(sim, *st, b, true);
       b.written++, b.last_final_cycle = c.ncycle;
     }
   }
@@ -246,6 +407,26 @@ int artemis_sim_enable_outputs(artemis_sim_t *sim, const char *dir) {
   }
 }
 
+int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single) {
+  using namespace artemis_out;
+  try {
+    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
+    const Clock c = clock_of(sim);
+    std::vector<int> codes;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = field_var_code(name);
+      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
+      codes.push_back(code);
+    }
+    write_fields(sim, path, codes, single != 0);
+    return 0;
+  } catch (const std::exception &e) {
+    artemis_ckpt::set_error(e.what());
+    return 1;
+  }
+}
+
 int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long capacity) {
   using namespace artemis_out;
   try {
@@ -264,7 +445,13 @@ int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long 
            ", \"dt\": " + json_num(b.dt) + ", \"status\": " + json_str(status_of(*st, b)) +
            ", \"next_time\": " + (live ? json_num(b.next_time) : "null") + ", \"written\": " + std::to_string(b.written) +
            ", \"last_cycle\": " + (b.last_cycle >= 0 ? std::to_string(b.last_cycle) : "null") +
-           ", \"path\": " + (b.path.empty() ? "null" : json_str(b.path)) + "}";
+           ", \"path\": " + (b.path.empty() ? "null" : json_str(b.path));
+      if (b.is_fld) {
+        j += ", \"variables\": [";
+        for (size_t v = 0; v < b.variables.size(); ++v) j += (v ? ", " : "") + json_str(b.variables[v]);
+        j += std::string("], \"single_precision\": ") + (b.single ? "true" : "false");
+      }
+      j += "}";
     }
     j += "]}";
     if (json_out && capacity > static_cast<long>(j.size())) std::memcpy(json_out, j.c_str(), j.size() + 1);

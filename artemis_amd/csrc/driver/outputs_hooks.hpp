@@ -27,13 +27,53 @@ const State *state_of(const artemis_sim_t *sim);
 // (artemis_hip_history_sums) where the library has it, the host sum otherwise
 int history_sums(artemis_sim_t *sim, double *out);
 
+// ---- field output ----------------------------------------------------------------------------------------------------
+// The variables a `fld` block may name, in the order of enum artemis_field_var (include/artemis_hip.h)
+constexpr int kFieldVars = 12;
+inline const char *field_var_name(int code) {
+  static const char *const names[kFieldVars] = {"gas.prim.density", "gas.prim.velocity", "gas.prim.pressure", "gas.prim.sie",
+                                                "gas.cons.density", "gas.cons.momentum", "gas.cons.total_energy",
+                                                "gas.cons.internal_energy", "dust.prim.density", "dust.prim.velocity",
+                                                "dust.cons.density", "dust.cons.momentum"};
+  return (code >= 0 && code < kFieldVars) ? names[code] : "";
+}
+inline int field_var_code(const std::string &name) { // -1: no such variable
+  for (int c = 0; c < kFieldVars; ++c)
+    if (name == field_var_name(c)) return c;
+  return -1;
+}
+inline bool field_var_is_dust(int code) { return code >= 8; }
+inline bool field_var_is_vector(int code) { return code == 1 || code == 5 || code == 9 || code == 11; }
+// components of a variable on a run with these species counts; 0: its fluid is absent
+inline int field_var_components(int code, int ns_gas, int ns_dust) {
+  return (field_var_is_vector(code) ? 3 : 1) * (field_var_is_dust(code) ? ns_dust : ns_gas);
+}
+
+struct FieldBlock { // one mesh block of the global mesh as meta.json lists it
+  long gid = 0;
+  int level = 0, rank = 0, index = 0; // index: its place among the blocks of `rank`
+  double bounds[6] = {0, 0, 0, 0, 0, 0};
+};
+struct FieldsLayout {
+  std::string coordinates;
+  int ndim = 0, nx[3] = {1, 1, 1}, rank = 0, nranks = 1;
+  double gamma = 0.0;
+  std::vector<FieldBlock> blocks; // every block of the mesh, in gid order
+};
+// (driver.cpp) the global block table: every rank contributes its rows (collective)
+FieldsLayout fields_layout(artemis_sim_t *sim);
+// (driver.cpp) this rank's blocks as [local block][component][nk][nj][ni] of interior zones, double or float: through
+// artemis_hip_pack_fields and a bounded staging buffer, or -- a library without that kernel -- a host loop over the
+// downloaded primitives.  host_out = NULL: nothing is gathered.  Returns the bytes of the gather.
+size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out);
+
 // ---- outputs.cpp -----------------------------------------------------------------------------------------------------
 void destroy(State *st);
 bool enabled(const State *st);
 // earliest next_time of a block that is acted on; +infinity without one
 double deadline(const State *st);
 // Write every block that is due at the simulation's clock (time >= next_time) and move its next_time on.  history_only:
-// called from inside the batched time loop, where a dump is not taken -- returns true if an `rst` block is still due, and
+// called from inside the batched time loop, where a dump is not taken -- returns true if an `rst` or `fld` block is still due, and
 // the loop then hands control back to the handle, which calls again with history_only = false.  Collective.
 bool write_due(artemis_sim_t *sim, bool history_only);
 // The run has ended at tlim or nlim: every block once more, unless this cycle has written it already.  Collective.

@@ -119,4 +119,12 @@ void launch_ml_floor_ghosts(const PackView &P, const int *blocks, int nblocks, h
 // kernels_history.hip: rows of partial sums the first launch writes (a function of the pack's shape alone)
 long history_workgroups(const PackView &P);
 void launch_history_sums(const PackView &P, double *sums, double *scratch, hipStream_t s);
+// kernels_fields.hip: the variables of artemis_hip_pack_fields as a kernel argument -- entry e holds variable code[e] and
+// its components start at component comp0[e] of a block's ncomp
+constexpr int FIELDS_MAX_SEL = 32;
+struct FieldSelection {
+  int nsel, ncomp, want_gas, want_dust;
+  int code[FIELDS_MAX_SEL], comp0[FIELDS_MAX_SEL];
+};
+void launch_pack_fields(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, void *out, hipStream_t s);
 } // namespace artemis

@@ -255,6 +255,9 @@ def _declare(L):
     L.artemis_sim_enable_outputs.argtypes = [vp, C.c_char_p]
     L.artemis_sim_history_device.argtypes = [vp, C.POINTER(d)]
     L.artemis_sim_outputs_describe.argtypes = [vp, C.c_char_p, l]
+    L.artemis_sim_gather_fields.restype = l
+    L.artemis_sim_gather_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp]
+    L.artemis_sim_write_fields.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i]
     L._sim_declared = True
 
 
@@ -479,7 +482,8 @@ class Simulation:
     def enable_outputs(self, directory):
         """Act on the deck's <parthenon/outputN> blocks from now on: `hst` blocks append rows to
         <directory>/<problem_id>.outN.hst (artemis_amd.history.read_history reads them), `rst` blocks save checkpoints to
-        <directory>/<problem_id>.outN.<counter>.rst (Simulation.restore reads them).  Output times never change dt."""
+        <directory>/<problem_id>.outN.<counter>.rst (Simulation.restore reads them), `fld` blocks write their `variables` to
+        <directory>/<problem_id>.outN.<counter>.fld (artemis_amd.fields.read_fields reads them).  Output times never change dt."""
         if self.L.artemis_sim_enable_outputs(self.h, os.fspath(directory).encode()):
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
 
@@ -493,6 +497,33 @@ class Simulation:
         if self.L.artemis_sim_outputs_describe(self.h, buf, n + 1) != n:
             raise RuntimeError("the output state changed while it was read")
         return json.loads(buf.value.decode())
+
+    @staticmethod
+    def _names(variables):
+        variables = [variables] if isinstance(variables, str) else list(variables)
+        return (C.c_char_p * max(len(variables), 1))(*[v.encode() for v in variables]), len(variables)
+
+    def gather(self, variables, single=False):
+        """The named variables ('gas.prim.density', 'gas.prim.velocity', 'gas.prim.pressure', ...: include/artemis_driver.h
+        "field output") of this rank's blocks, interior zones only, as [nblocks_local, ncomp, nz, ny, nx] float64 (float32
+        with single=True).  Formed from the primitives on the device; nothing is materialised and the run is not disturbed."""
+        names, n = self._names(variables)
+        nbytes = self.L.artemis_sim_gather_fields(self.h, n, names, int(single), None)
+        if nbytes < 0:
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+        self._refresh_dims()
+        out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
+        ncomp = self.L.artemis_sim_gather_fields(self.h, n, names, int(single), out.ctypes.data)
+        if ncomp < 0:
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+        return out.reshape(self.nblocks, ncomp, self.ke - self.ks + 1, self.je - self.js + 1, self.ie - self.is_ + 1)
+
+    def write_fields(self, path, variables, single=False):
+        """One dump of the named variables as a directory at `path` (collective over the ranks of the run; replaces an
+        existing one).  artemis_amd.fields.read_fields reads it."""
+        names, n = self._names(variables)
+        if self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single)):
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
 
     def errors(self):
         o = (C.c_double * 16)()

@@ -200,6 +200,13 @@ void artemis_sim_checkpoint_seconds(double *out4);
  *                     step's).  An existing file is appended to behind a fresh header section.  Rank 0 writes.
  *   file_type = rst   artemis_sim_save into <dir>/<problem_id>.outN.<5-digit counter>.rst, and into ...outN.final.rst
  *                     when the run ends.
+ *   file_type = fld   artemis_sim_write_fields ("field output" below) of the block's `variables` (comma list) into
+ *                     <dir>/<problem_id>.outN.<5-digit counter>.fld, and into ...outN.final.fld when the run ends; scheduled
+ *                     and numbered like `rst`.  single_precision_output = true (parthenon's key) stores float.  A block
+ *                     without `variables`, with a name outside the list or of a fluid the run lacks, or with ghost_zones
+ *                     = true is listed as skipped ("no variables", "unknown variable NAME", "ghost_zones is not built") and
+ *                     writes nothing.  A shipped `hdf5` block becomes one with the override
+ *                     parthenon/outputN/file_type=fld.
  *   anything else     not acted on (never an error); artemis_sim_outputs_describe lists it as skipped.
  * Schedule (parthenon's Outputs, upstream): a block is due after the first cycle that ends with time >= next_time, and
  * next_time then becomes the smallest integer multiple of the block's dt above time; a fresh run writes every block at
@@ -212,9 +219,35 @@ int artemis_sim_enable_outputs(artemis_sim_t *sim, const char *dir);
  * (the layout of artemis_sim_history for one gas species).  Returns the number of values, < 0 on error. */
 int artemis_sim_history_device(artemis_sim_t *sim, double *out);
 /* The output blocks of the deck and their state as one JSON object {"enabled", "dir", "problem_id", "blocks": [{"block",
- * "index", "file_type", "dt", "status", "next_time", "written", "last_cycle", "path"}]}.  Returns the length of the text
+ * "index", "file_type", "dt", "status", "next_time", "written", "last_cycle", "path"}]}; a `fld` block also has
+ * "variables" (the names of its list) and "single_precision".  Returns the length of the text
  * (written with its NUL only if capacity exceeds it: call with NULL / 0 for the size), < 0 on error. */
 int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long capacity);
+
+/* ---- field output --------------------------------------------------------------------------------------------------
+ * Variables are named as in a deck's `variables` line: gas.prim.density | .velocity | .pressure | .sie, gas.cons.density |
+ * .momentum | .total_energy | .internal_energy, dust.prim.density | .velocity, dust.cons.density | .momentum.  A scalar has
+ * one component per species, a vector three (index 3 n + d).  Every value is what PrimToCons would store for the zone
+ * (floors applied; the pressure is (gamma-1) rho sie, not the stored slot, which the one-kernel stages never write), formed
+ * from the primitives on the device (artemis_hip_pack_fields): no conserved array is materialised and the run's bits do
+ * not change.
+ *
+ * gather: host_out receives [local block][component][nk][nj][ni] over the INTERIOR zones of this rank's blocks, the
+ * components in the order of `names`, as double or (single != 0) float; returns the number of components.  host_out =
+ * NULL: returns the size of that buffer in bytes and gathers nothing.  The device side is a staging buffer of a whole
+ * number of blocks and at most 256 MiB (switch FIELDS_STAGE_MB, artemis_hip.h), allocated by the first call.  A name
+ * outside the list, or of a fluid the run does not have, is an error: < 0 (artemis_sim_last_error()). */
+long artemis_sim_gather_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, void *host_out);
+/* write: one dump of those variables as a directory `path` (collective; the ranks must see one file system):
+ *   meta.json     {"format": "artemis_fld", "version": 1, "time", "dt", "cycle", "coordinates", "ndim", "nghost": 0,
+ *                 "dtype": "<f8" | "<f4", "gamma", "ns_gas", "ns_dust", "nranks", "nx": [nx1, nx2, nx3] of a block,
+ *                 "variables": [{"name", "ncomp", "components": [names]}], "blocks": [{"gid", "level", "bounds": [x1min,
+ *                 x1max, x2min, x2max, x3min, x3max], "nx", "rank", "index"}] in gid order}; rank 0 writes it, last
+ *   rank<r>.bin   the raw little-endian gather of rank r: block `index` of rank `rank` starts at index * ncomp * nx1 *
+ *                 nx2 * nx3 elements
+ * Everything is written into <path>.tmp, which is renamed once every rank has succeeded (an existing dump at `path` is
+ * replaced): a directory that is there is complete.  artemis_amd/fields.py reads it.  Returns 0, non-zero on error. */
+int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single);
 
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured

@@ -83,6 +83,8 @@
  *                    shows up as NaN instead of whatever the allocator returned)
  *    DENSE_FLUX      the standalone driver gives every block of a refined mesh its flux arrays on the one-kernel stages
  *                    too (default: rows only for the blocks that own a coarse-fine face, the only place they are used)
+ *    FIELDS_STAGE_MB=n  the standalone driver's field gather (artemis_sim_gather_fields) stages at most n MiB on the device
+ *                    at a time (default 256; always a whole number of blocks, one block where a block is larger) -- same bits
  * ===================================================================================== */
 #ifndef ARTEMIS_HIP_H_
 #define ARTEMIS_HIP_H_
@@ -237,6 +239,32 @@ int artemis_hip_estimate_dt_async(const artemis_pack_t *p, int fluid, double cfl
  * run and every device.  Asynchronous on `stream`. */
 size_t artemis_hip_history_scratch_bytes(const artemis_pack_t *p);
 int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_dev, double *scratch_dev, void *stream);
+
+/* Field output: the variables an output block names (parthenon's `variables = gas.prim.density, ...`), formed from p's
+ * PRIMITIVES for every interior zone and packed ghost-free.  A variable has nspecies components, a vector 3 * nspecies in
+ * the reference's VI order 3n + d:
+ *   gas.prim.density, .velocity, .pressure, .sie; gas.cons.density, .momentum, .total_energy, .internal_energy;
+ *   dust.prim.density, .velocity; dust.cons.density, .momentum. */
+enum artemis_field_var { ARTEMIS_VAR_GAS_PRIM_DENSITY = 0, ARTEMIS_VAR_GAS_PRIM_VELOCITY = 1, ARTEMIS_VAR_GAS_PRIM_PRESSURE = 2,
+                         ARTEMIS_VAR_GAS_PRIM_SIE = 3, ARTEMIS_VAR_GAS_CONS_DENSITY = 4, ARTEMIS_VAR_GAS_CONS_MOMENTUM = 5,
+                         ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY = 6, ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY = 7,
+                         ARTEMIS_VAR_DUST_PRIM_DENSITY = 8, ARTEMIS_VAR_DUST_PRIM_VELOCITY = 9, ARTEMIS_VAR_DUST_CONS_DENSITY = 10,
+                         ARTEMIS_VAR_DUST_CONS_MOMENTUM = 11, ARTEMIS_VAR_COUNT = 12 };
+/* artemis_hip_pack_fields fills out_dev (DEVICE) with [block - block0][component][k][j][i] over the interior zones of
+ * blocks [block0, block0 + nblocks), the components in the order of the nsel codes of `sel` (HOST array, at most 32
+ * entries; a code may repeat), as double or -- single != 0 -- as float.  Every value is the double PrimToCons
+ * (fill_derived.cpp:212-276) would leave in that slot: dfloor / siefloor applied to rho and sie, P = max(0, (gamma-1) rho
+ * sie), M_d = rho v_d h_d with the scale factors of the pack's coordinates, eint = rho sie, E = eint + rho v^2 / 2, in the
+ * expressions and operation order of artemis_hip_prim_to_cons; the float form is that double rounded to nearest.  No
+ * conserved array and no stored pressure is read and nothing is written to the pack, so the stored pressure may be stale
+ * (the one-kernel stages never write it) and `cons` need not exist.  Offsets into out_dev are 64-bit.  An unknown code, a
+ * dust code on a pack without dust (or a gas code without gas), nblocks < 0 or a block range outside the pack return
+ * ARTEMIS_HIP_EINVAL.  Asynchronous on `stream`.
+ * artemis_hip_pack_fields_bytes: the bytes all p->nblocks blocks take (a range takes nblocks / p->nblocks of it); 0 for
+ * arguments pack_fields would refuse. */
+size_t artemis_hip_pack_fields_bytes(const artemis_pack_t *p, int nsel, const int *sel, int single);
+int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                            void *out_dev, void *stream);
 
 /* Metric tables.  geometry::Coords<GEOM> evaluates transcendentals per cell: for spherical 2-D/3-D
  * cos/sin of the x2 faces, the x2 centroid and the x2 midpoint (spherical.hpp:61-146); for
