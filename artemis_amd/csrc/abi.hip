@@ -292,6 +292,21 @@ int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, in
   artemis::launch_pack_fields(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, out_dev, S(stream));
   return after_launch("pack_fields");
 }
+int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                              const void *in_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldUnpack U;
+  const std::string bad = artemis::field_unpack_plan(nsel, sel, p->gas.nspecies, p->dust.nspecies, U);
+  if (!bad.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", bad.c_str());
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
+    return fail(ARTEMIS_HIP_EINVAL, "unpack fields: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
+  if ((U.gas_form && !p->gas.prim) || (U.dust_form && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "unpack fields: the primitive tables of the fluids named are required");
+  if (nblocks == 0 || U.ncomp == 0) return 0;
+  if (!in_dev) return fail(ARTEMIS_HIP_EINVAL, "unpack fields: null in_dev");
+  artemis::launch_unpack_fields(artemis::make_pack_view(*p), block0, nblocks, U, single != 0, in_dev, S(stream));
+  return after_launch("unpack_fields");
+}
 
 int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, double *dt_out,
                             void *stream) {

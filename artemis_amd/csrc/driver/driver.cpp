@@ -28,6 +28,7 @@
 #include "artemis_hip.h"
 #include "artemis_rt.h"
 #include "../geometry_core.hpp"
+#include "../fields_form.hpp"
 #include "parameter_input.hpp"
 #include "block_tree.hpp"
 #include "checkpoint_hooks.hpp"
@@ -41,6 +42,9 @@ extern "C" int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_de
 // ... and so is the kernel of the field outputs: without it the gather forms the same expressions in a host loop
 extern "C" int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                        void *out_dev, void *stream) __attribute__((weak));
+// ... and its inverse, which artemis_sim_scatter_fields sets a state with: without it the same expressions in a host loop
+extern "C" int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                         const void *in_dev, void *stream) __attribute__((weak));
 static_assert(artemis_out::kFieldVars == ARTEMIS_VAR_COUNT, "outputs_hooks.hpp names every artemis_field_var");
 
 #define SQR(x) ((x) * (x))
@@ -494,6 +498,8 @@ struct artemis_sim_impl {
   // most FIELDS_STAGE_MB (default 256) MiB, one block where a block is larger; allocated by the first gather
   DevBuf field_stage;
   size_t gather_fields(const std::vector<int> &codes, bool single, void *host_out);
+  // artemis_sim_scatter_fields: the inverse, through the same staging buffer, then the sequence a problem generator ends with
+  size_t scatter_fields(const std::vector<int> &codes, bool single, const void *host_in, double new_time);
   int errors(double *out);
 };
 
@@ -3608,6 +3614,117 @@ size_t artemis_sim_impl::gather_fields(const std::vector<int> &codes, bool singl
   return static_cast<size_t>(nb) * block_bytes;
 }
 
+// The inverse of gather_fields: `host_in` holds one complete form of the state per fluid (fields_form.hpp) for this rank's
+// interior zones, laid out as gather_fields returns it.  The primitives of the current buffer are written from it -- by
+// artemis_hip_unpack_fields out of the staging buffer, one copy per block range, or in a host loop with the same expressions
+// where the library lacks that kernel -- and then the state is completed as a problem generator's is (problem_generator's
+// last lines): PrimToCons, ConsToPrim, the ghost fill, PrimToCons.  dt becomes a fresh estimate, as ensure_first_dt's.
+// Collective.  host_in = NULL: validates only.  Returns the bytes of the buffer.
+size_t artemis_sim_impl::scatter_fields(const std::vector<int> &codes, bool single, const void *host_in, double new_time) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  artemis::FieldUnpack U;
+  const std::string bad = artemis::field_unpack_plan(static_cast<int>(codes.size()), codes.data(), nsg, nsd, U);
+  if (!bad.empty()) throw std::runtime_error("scatter_fields: " + bad);
+  for (int d = 0; d < ndim; ++d)
+    if (mbnx[d] < ng)
+      throw std::runtime_error("scatter_fields: blocks of " + std::to_string(mbnx[d]) + " zones along x" + std::to_string(d + 1) +
+                               " are narrower than the " + std::to_string(ng) + " ghost zones: the state of such a run is all three "
+                               "primitive buffers, which a scatter of one does not set");
+  const size_t zones = static_cast<size_t>(mbnx[0]) * mbnx[1] * mbnx[2], esz = single ? sizeof(float) : sizeof(double);
+  const size_t block_bytes = static_cast<size_t>(U.ncomp) * zones * esz;
+  if (!host_in) return static_cast<size_t>(nb) * block_bytes;
+  if (block_bytes != 0 && artemis_hip_unpack_fields) {
+    const artemis_pack_t p = make_pack(base);
+    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
+    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
+    const int per = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(nb), cap / block_bytes)));
+    const size_t need = (static_cast<size_t>(per) * block_bytes + sizeof(double) - 1) / sizeof(double);
+    if (field_stage.n < need) field_stage.alloc(need);
+    for (int b0 = 0; b0 < nb; b0 += per) {
+      const int n = std::min(per, nb - b0);
+      CK(artemis_rt_memcpy_h2d(field_stage.p, static_cast<const char *>(host_in) + static_cast<size_t>(b0) * block_bytes,
+                               static_cast<size_t>(n) * block_bytes, stream), "h2d");
+      CK(artemis_hip_unpack_fields(&p, b0, n, static_cast<int>(codes.size()), codes.data(), single ? 1 : 0, field_stage.p, stream), "unpack fields");
+      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffer)
+    }
+  } else if (block_bytes != 0) {
+    for (int b = 0; b < nb; ++b) {
+      std::vector<Real> g, d;
+      if (U.gas_form) g = download(gprim[base], b);
+      if (U.dust_form) d = download(dprim[base], b);
+      const char *ib = static_cast<const char *>(host_in) + static_cast<size_t>(b) * block_bytes;
+      for (int k = ks; k <= ke; ++k)
+        for (int j = js; j <= je; ++j)
+          for (int i = is; i <= ie; ++i) {
+            const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
+            const size_t z = (static_cast<size_t>(k - ks) * mbnx[1] + (j - js)) * mbnx[0] + (i - is);
+            auto get = [&](int comp) {
+              return single ? static_cast<Real>(reinterpret_cast<const float *>(ib)[comp * zones + z])
+                            : reinterpret_cast<const double *>(ib)[comp * zones + z];
+            };
+            Real hx[3] = {1.0, 1.0, 1.0}; // GetScaleFactors (geometry.hpp:384-388)
+            if (coords != ARTEMIS_CARTESIAN) {
+              const artemis::DCoords co = cell_coords(b, k, j, i);
+              hx[1] = co.hx2v(), hx[2] = co.hx3v();
+            }
+            for (int n = 0; n < (U.gas_form ? nsg : 0); ++n) { // unpack_fields_kernel's expressions (kernels_fields.hip)
+              const Real D = get(U.g_rho + n);
+              const Real w_d = (D > dfloor_gas) ? D : dfloor_gas;
+              const Real a[3] = {get(U.g_vec + 3 * n + 0), get(U.g_vec + 3 * n + 1), get(U.g_vec + 3 * n + 2)};
+              const Real en = get(U.g_en + n);
+              Real vel[3] = {a[0], a[1], a[2]}, w_s = en;
+              if (U.gas_form == artemis::FORM_PRIM_PRESSURE) {
+                w_s = en / ((gamma - 1.0) * w_d);
+              } else if (U.gas_form == artemis::FORM_CONS) { // SetAuxillaryFields (fill_derived.cpp:54-73) ...
+                const Real u_d2 = std::max(D, dfloor_gas);
+                const Real rv[3] = {a[0] / hx[0], a[1] / hx[1], a[2] / hx[2]};
+                const Real ke = 0.5 * (SQR(rv[0]) + SQR(rv[1]) + SQR(rv[2])) / u_d2;
+                const Real ue_cons = en - ke;
+                const Real eg = (U.g_eint >= 0) ? get(U.g_eint + n) : 0.0;
+                Real sie = (ue_cons > de_switch * en) ? ue_cons / u_d2 : eg / u_d2;
+                sie = std::max(sie, siefloor_gas);
+                Real u_u = sie * w_d;
+                const Real uflr = siefloor_gas * w_d;
+                u_u = (u_u > uflr) ? u_u : uflr;
+                for (int q = 0; q < 3; ++q) vel[q] = a[q] / (w_d * hx[q]); // ... then ConsToPrim (fill_derived.cpp:120-166)
+                w_s = u_u / w_d;
+              }
+              w_s = (w_s > siefloor_gas) ? w_s : siefloor_gas;
+              g[n * N + c] = w_d;
+              for (int q = 0; q < 3; ++q) g[(nsg + 3 * n + q) * N + c] = vel[q];
+              g[(5 * nsg + n) * N + c] = w_s;
+            }
+            for (int m = 0; m < (U.dust_form ? nsd : 0); ++m) {
+              const Real D = get(U.d_rho + m);
+              const Real w_d = (D > dfloor_dust) ? D : dfloor_dust;
+              d[m * N + c] = w_d;
+              for (int q = 0; q < 3; ++q) {
+                const Real a = get(U.d_vec + 3 * m + q);
+                d[(nsd + 3 * m + q) * N + c] = (U.dust_form == artemis::FORM_CONS) ? a / (w_d * hx[q]) : a;
+              }
+            }
+          }
+      if (U.gas_form) upload_block(gprim[base], b, g);
+      if (U.dust_form) upload_block(dprim[base], b, d);
+    }
+  }
+  const artemis_pack_t p = make_pack(base);
+  CK(artemis_hip_prim_to_cons(&p, stream), "PrimToCons");
+  CK(artemis_hip_cons_to_prim(&p, stream), "ConsToPrim");
+  fill_ghosts(base);
+  CK(artemis_hip_prim_to_cons(&p, stream), "PrimToCons");
+  // every zone of the current buffer is now what the conditions and the neighbours make of the new interior: nothing a
+  // stage loop left for later (fill_stale_ghosts) or remembered about the old state (the tuned kernel's hint words) holds
+  cons_valid = true, ghosts_stale = false, tiny_valid = false;
+  CK(artemis_rt_stream_sync(stream), "sync");
+  if (!std::isnan(new_time)) time = new_time;
+  Real est = new_dt_unfused();
+  if (has_comm && nranks > 1 && comm.allreduce_min(comm.ctx, &est)) throw std::runtime_error("allreduce failed");
+  dt = est;
+  if (tlim > 0.0 && time < tlim && (tlim - time) < dt) dt = tlim - time;
+  return static_cast<size_t>(nb) * block_bytes;
+}
+
 // linear_wave.hpp:267-377 / advection.hpp:224-405 UserWorkAfterLoop
 int artemis_sim_impl::errors(double *out) {
   if (pgen != PG_LINWAVE && pgen != PG_ADVECTION) return 0;
@@ -4050,6 +4167,9 @@ const State *state_of(const artemis_sim_t *sim) { return sim->outputs; }
 int history_sums(artemis_sim_t *sim, double *out) { return sim->p->history_device(out); }
 size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out) {
   return sim->p->gather_fields(codes, single, host_out);
+}
+size_t scatter_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, const void *host_in, double time) {
+  return sim->p->scatter_fields(codes, single, host_in, time);
 }
 FieldsLayout fields_layout(artemis_sim_t *sim) {
   const artemis_sim_impl &S = *sim->p;

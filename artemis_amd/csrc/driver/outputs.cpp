@@ -427,6 +427,27 @@ int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, con
   }
 }
 
+long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in, double time) {
+  using namespace artemis_out;
+  try {
+    if (!sim) throw std::runtime_error("scatter_fields: no simulation");
+    const std::string dead = artemis_ckpt::dead_reason(sim);
+    if (!dead.empty()) throw std::runtime_error(dead);
+    const Clock c = clock_of(sim);
+    std::vector<int> codes;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = field_var_code(name);
+      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("scatter_fields: unknown variable " + name);
+      codes.push_back(code);
+    }
+    return static_cast<long>(scatter_fields(sim, codes, single != 0, host_in, time));
+  } catch (const std::exception &e) {
+    artemis_ckpt::set_error(e.what());
+    return -1;
+  }
+}
+
 int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long capacity) {
   using namespace artemis_out;
   try {

@@ -66,6 +66,11 @@ FieldsLayout fields_layout(artemis_sim_t *sim);
 // artemis_hip_pack_fields and a bounded staging buffer, or -- a library without that kernel -- a host loop over the
 // downloaded primitives.  host_out = NULL: nothing is gathered.  Returns the bytes of the gather.
 size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out);
+// (driver.cpp) the inverse: host_in in that layout, holding one complete form of the state per fluid (csrc/fields_form.hpp),
+// becomes the interior primitives of the current buffer -- artemis_hip_unpack_fields out of the same staging buffer, or the
+// host loop -- and the state is completed as a problem generator's is; time = NaN keeps the clock, dt is estimated afresh.
+// host_in = NULL: validates only.  Collective.  Returns the bytes of the buffer.
+size_t scatter_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, const void *host_in, double time);
 
 // ---- outputs.cpp -----------------------------------------------------------------------------------------------------
 void destroy(State *st);

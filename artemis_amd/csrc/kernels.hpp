@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "fields_form.hpp"
 #include "pack_view.hpp"
 #include "stage_plan.hpp"
 
@@ -127,4 +128,6 @@ struct FieldSelection {
   int code[FIELDS_MAX_SEL], comp0[FIELDS_MAX_SEL];
 };
 void launch_pack_fields(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, void *out, hipStream_t s);
+// ... and its inverse: the form of each fluid that the buffer holds (fields_form.hpp) written to the interior primitives
+void launch_unpack_fields(const PackView &P, int block0, int nblocks, const FieldUnpack &U, bool single, const void *in, hipStream_t s);
 } // namespace artemis

@@ -258,6 +258,8 @@ def _declare(L):
     L.artemis_sim_gather_fields.restype = l
     L.artemis_sim_gather_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp]
     L.artemis_sim_write_fields.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i]
+    L.artemis_sim_scatter_fields.restype = l
+    L.artemis_sim_scatter_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp, d]
     L._sim_declared = True
 
 
@@ -524,6 +526,101 @@ class Simulation:
         names, n = self._names(variables)
         if self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single)):
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
+
+    def scatter(self, variables, array, time=None):
+        """The inverse of gather: the run takes its state from `array`, [nblocks_local, ncomp, nz, ny, nx] float64 or float32,
+        C-contiguous, laid out as gather(variables) returns it.  For each fluid the variables give one complete form or
+        nothing: gas.prim.density + .velocity + one of .sie / .pressure, or gas.cons.density + .momentum + .total_energy
+        (+ .internal_energy); dust.prim.density + .velocity, or dust.cons.density + .momentum.  The ghost zones are filled
+        and the conserved state formed as after a problem generator, `time` becomes the clock (None keeps it) and dt a fresh
+        estimate; ncycle, the mesh and the output schedule stay.  Collective over the ranks of the run.  ValueError for an
+        array of the wrong shape, dtype or layout, RuntimeError for what the driver refuses."""
+        names, n = self._names(variables)
+        if not isinstance(array, np.ndarray) or array.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("scatter takes a numpy array of float64 or float32, not %s"
+                             % (array.dtype if isinstance(array, np.ndarray) else type(array).__name__))
+        if not array.flags["C_CONTIGUOUS"]:
+            raise ValueError("scatter takes a C-contiguous array")
+        single = array.dtype == np.float32
+        listed = [variables] if isinstance(variables, str) else list(variables)
+        species = {"gas": self.ns_gas, "dust": self.ns_dust}
+        # (a name outside the list, or of a fluid the run lacks, is the driver's to refuse)
+        if all(v in capi.FIELD_VAR and species[v.split(".")[0]] > 0 for v in listed):
+            self._refresh_dims()
+            ncomp = sum((3 if v.endswith(("velocity", "momentum")) else 1) * (self.ns_dust if v.startswith("dust.") else self.ns_gas)
+                        for v in listed)
+            want = (self.nblocks, ncomp, self.ke - self.ks + 1, self.je - self.js + 1, self.ie - self.is_ + 1)
+            if tuple(array.shape) != want:
+                raise ValueError("scatter: the array is %s, these variables on this rank's blocks are %s" % (tuple(array.shape), want))
+        t = float("nan") if time is None else float(time)
+        if self.L.artemis_sim_scatter_fields(self.h, n, names, int(single), array.ctypes.data, t) < 0:
+            raise RuntimeError(self.L.artemis_sim_last_error().decode())
+
+    # the complete forms a dump may hold, in the order load_fields prefers them
+    _GAS_FORMS = (("gas.prim.density", "gas.prim.velocity", "gas.prim.sie"),
+                  ("gas.prim.density", "gas.prim.velocity", "gas.prim.pressure"),
+                  ("gas.cons.density", "gas.cons.momentum", "gas.cons.total_energy"))
+    _DUST_FORMS = (("dust.prim.density", "dust.prim.velocity"), ("dust.cons.density", "dust.cons.momentum"))
+
+    def _agree(self, problem):
+        """Raise on every rank if any rank has a problem (a rank that raised alone would leave the others in a collective)."""
+        if self.comm is not None and self.comm.struct.nranks > 1:
+            v = C.c_double(0.0 if problem else 1.0)
+            if self.comm.struct.allreduce_min(self.comm.struct.ctx, C.byref(v)):
+                raise RuntimeError("allreduce failed")
+            if problem is None and v.value == 0.0:
+                problem = "load_fields: another rank could not take its blocks from the dump"
+        if problem:
+            raise ValueError(problem)
+
+    def load_fields(self, path, clock=True):
+        """Start from a `fld` dump (write_fields, or a deck's fld block): its blocks are matched to this rank's by level and
+        bounds, so a dump written on any number of ranks loads on any other, and scatter() takes whichever complete form
+        the dump holds of each fluid -- primitives with sie first, then primitives with the pressure, then the conserved
+        variables.  clock=True also takes the dump's time.  ValueError names the first block of this rank the dump lacks,
+        or the first variable missing for a complete form.  Collective.  Returns the variables taken."""
+        from .fields import read_fields
+        fd = read_fields(path)
+        have = set(fd.variables)
+        names = []
+        for fluid, ns, forms in (("gas", self.ns_gas, self._GAS_FORMS), ("dust", self.ns_dust, self._DUST_FORMS)):
+            mine = sorted(v for v in have if v.startswith(fluid + "."))
+            if not mine:
+                continue
+            if ns == 0:
+                raise ValueError("%s holds %s, and this run has no %s" % (path, mine[0], fluid))
+            form = next((f for f in forms if have.issuperset(f)), None)
+            if form is None:  # the form the dump is closest to, and what it lacks first
+                near = max(forms, key=lambda f: sum(v in have for v in f))
+                lacking = next(v for v in near if v not in have)
+                if lacking in ("gas.prim.sie", "gas.prim.pressure"):
+                    lacking = "gas.prim.sie (or gas.prim.pressure)"
+                raise ValueError("%s holds %s: %s is missing for a complete form" % (path, ", ".join(mine), lacking))
+            names += list(form)
+            if form[0] == "gas.cons.density" and "gas.cons.internal_energy" in have:
+                names.append("gas.cons.internal_energy")
+            for v in form:
+                if fd.variables[v] != (3 if v.endswith(("velocity", "momentum")) else 1) * ns:
+                    raise ValueError("%s: %s has %d components, this run %d species" % (path, v, fd.variables[v], ns))
+        if not names:
+            raise ValueError("%s holds no variable of this run's fluids" % path)
+        self._refresh_dims()
+        nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
+        problem, gids = None, []
+        if list(fd.nx) != nx:
+            problem = "%s: its blocks are %s zones, this run's %s" % (path, list(fd.nx), nx)
+        where = {(b["level"], tuple(b["bounds"])): g for g, b in enumerate(fd.blocks)}
+        for b in range(self.nblocks if problem is None else 0):
+            key = (self.block_level(b), tuple(self.block_bounds(b)))
+            if key not in where:
+                problem = "%s holds no block on level %d with the bounds %s (local block %d of this run)" % (path, key[0], list(key[1]), b)
+                break
+            gids.append(where[key])
+        self._agree(problem)
+        array = np.concatenate([fd.get(v)[gids] for v in names], axis=1) if gids else \
+            np.empty((0, sum(fd.variables[v] for v in names), nx[2], nx[1], nx[0]), dtype=fd.dtype)
+        self.scatter(names, np.ascontiguousarray(array), time=fd.time if clock else None)
+        return names
 
     def errors(self):
         o = (C.c_double * 16)()

@@ -248,6 +248,27 @@ long artemis_sim_gather_fields(artemis_sim_t *sim, int nvar, const char *const *
  * Everything is written into <path>.tmp, which is renamed once every rank has succeeded (an existing dump at `path` is
  * replaced): a directory that is there is complete.  artemis_amd/fields.py reads it.  Returns 0, non-zero on error. */
 int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single);
+/* scatter: the inverse of gather -- the run takes its state from the caller's arrays, which is this driver's form of
+ * "write your own problem generator".  host_in is this rank's blocks in local order, laid out as gather returns them for
+ * the same names ([local block][component][nk][nj][ni] over the INTERIOR zones, double or float).  For each fluid the names
+ * give exactly one complete form, or nothing (that fluid keeps its state); each name once:
+ *   gas    gas.prim.density + .velocity + one of .sie / .pressure, or gas.cons.density + .momentum + .total_energy
+ *          (+ .internal_energy; without it that input is 0 and gas/de_switch decides as in SetAuxillaryFields)
+ *   dust   dust.prim.density + .velocity, or dust.cons.density + .momentum
+ * (artemis_hip_unpack_fields, artemis_hip.h, has the expressions).  The arrays go through the staging buffer of gather, a
+ * whole number of blocks per copy, into the interior primitives of the current buffer; then the state is completed the
+ * way a problem generator's is: PrimToCons, ConsToPrim, the ghost fill (neighbours, coarse-fine boundaries, physical
+ * conditions), PrimToCons.  `time` becomes the clock (NaN keeps it) and dt a fresh estimate as at the start of a run: the
+ * minimum over the ranks, clipped to tlim, without the "at most doubles" rule of a running clock.  ncycle, the mesh (no
+ * remesh happens here: the next cycle's tagging adapts it), the n-body rows, the output schedule and the initial-condition
+ * states of `ic` boundaries stay as they are; ghost zones no condition or neighbour writes (corners, on runs without
+ * viscosity) keep their old values, which nothing reads.
+ * host_in = NULL: validates the arguments and returns the size of that buffer in bytes, the number gather returns for them.
+ * Collective.  Returns that size, or < 0 (artemis_sim_last_error()): a dead handle, an unknown name or one of a fluid the
+ * run lacks, a mixed, incomplete or repeated form, or blocks narrower than nghost -- the state of such a run is all three
+ * primitive buffers (checkpoints store them), which one set of arrays does not give. */
+long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in,
+                                double time);
 
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured

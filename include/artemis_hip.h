@@ -265,6 +265,27 @@ enum artemis_field_var { ARTEMIS_VAR_GAS_PRIM_DENSITY = 0, ARTEMIS_VAR_GAS_PRIM_
 size_t artemis_hip_pack_fields_bytes(const artemis_pack_t *p, int nsel, const int *sel, int single);
 int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                             void *out_dev, void *stream);
+/* The inverse: in_dev (DEVICE) holds what artemis_hip_pack_fields writes for the same arguments -- [block - block0]
+ * [component][k][j][i] over the interior zones, the components in the order of the codes of `sel`, double or (single != 0)
+ * float, widened exactly -- and the PRIMITIVES of the interior zones of blocks [block0, block0 + nblocks) are written from
+ * it.  Every value stored is the one PrimToCons would leave in its slot: rho and sie floored for gas, rho floored for dust,
+ * velocities as given; a PrimToCons behind the call changes none of them.  The pressure slot, the conserved arrays and the
+ * ghost zones are NOT written.  For each fluid `sel` names exactly one complete form, or nothing (the fluid then stays
+ * untouched); each code at most once:
+ *   gas, primitive   gas.prim.density + gas.prim.velocity + exactly one of gas.prim.sie / gas.prim.pressure.  From a
+ *                    pressure, sie = P / ((gamma-1) rho) with the floored rho -- the product first, as pack_fields forms
+ *                    (gamma-1) rho sie, one correctly rounded division -- and then the sie floor.  pack_fields of the
+ *                    result returns P to within two roundings (2^-51 relative) where no floor binds.
+ *   gas, conserved   gas.cons.density + gas.cons.momentum + gas.cons.total_energy (+ gas.cons.internal_energy): what
+ *                    artemis_hip_set_aux followed by artemis_hip_cons_to_prim leave in the zone (fill_derived.cpp:30-75,
+ *                    :82-167), same expressions and operation order -- de_switch, the floors and the scale factors of the
+ *                    pack's coordinates included.  Without gas.cons.internal_energy that input is 0 in every zone.
+ *   dust             dust.prim.density + dust.prim.velocity, or dust.cons.density + dust.cons.momentum.
+ * Offsets into in_dev are 64-bit.  A mixed or incomplete form, a repeated or unknown code, a dust code on a pack without
+ * dust (or a gas code without gas), nblocks < 0 or a block range outside the pack return ARTEMIS_HIP_EINVAL, the cause in
+ * artemis_hip_last_error(), and write nothing.  Asynchronous on `stream`. */
+int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                              const void *in_dev, void *stream);
 
 /* Metric tables.  geometry::Coords<GEOM> evaluates transcendentals per cell: for spherical 2-D/3-D
  * cos/sin of the x2 faces, the x2 centroid and the x2 midpoint (spherical.hpp:61-146); for
