@@ -72,9 +72,15 @@ namespace {
 #endif
 // Flat-wave skip of the Cartesian march: work whose result a whole wave discards is not done.
 // 0 = off; 1 = one wave-uniform guard per slope and one per HLLC face; 2 = one guard per direction (the six slopes of
-// a sweep together) and one per HLLC face.  Same bits in every setting.
+// a sweep together) and one per HLLC face; 3 (the default, chosen by measurement: DESIGN.md section 7) = two levels: the
+// direction's guard first -- its flat side is straight-line code, q - 0.0 and q + 0.0 -- and behind it the unguarded
+// slopes (ARTEMIS_FLAT_SKIP_INNER = 0, the default) or the per-slope guards of form 1 (= 1); one guard per HLLC face.
+// Same bits in every setting.
 #ifndef ARTEMIS_FLAT_SKIP
-#define ARTEMIS_FLAT_SKIP 1
+#define ARTEMIS_FLAT_SKIP 3
+#endif
+#ifndef ARTEMIS_FLAT_SKIP_INNER
+#define ARTEMIS_FLAT_SKIP_INNER 0
 #endif
 #ifndef ARTEMIS_FTY
 #define ARTEMIS_FTY 8
@@ -263,7 +269,16 @@ ADEV void stage_plane_flag(TILE &S, const Ctx &x, const Cell6 &q, const Raw5 &ha
   if (x.hr >= 0) t = t || tiny_vel3(hal.v1, hal.v2, hal.v3);
   if (__any(t) && (x.t & 63) == 0) tiny_flag(S, par) = 1;
 }
+// ... with the own cell's verdict already known (the 3-D march of the Cartesian stage tested that cell one trip earlier,
+// as plane k + 2 of its own column): only the halo cell is tested
+template <class TILE>
+ADEV void stage_plane_flag_halo(TILE &S, const Ctx &x, const bool own, const Raw5 &hal, int par) {
+  bool t = own;
+  if (x.hr >= 0) t = t || tiny_vel3(hal.v1, hal.v2, hal.v3);
+  if (__any(t) && (x.t & 63) == 0) tiny_flag(S, par) = 1;
+}
 ADEV bool tiny_v(const Cell6 &q) { return tiny_vel3(q.v1, q.v2, q.v3); }
+ADEV int plm_flat_i(double qm, double q, double qp) { return plm_flat(qm, q, qp) ? 1 : 0; } // (to be combined with `&`)
 
 // x1/x2 sweeps of one plane through LDS.  Plane k's primitives are already staged in S.Q (by
 // the previous plane's call, or by the prologue).  TWO barriers per plane:
@@ -280,11 +295,15 @@ ADEV bool tiny_v(const Cell6 &q) { return tiny_vel3(q.v1, q.v2, q.v3); }
 template <int RIEMANN, int RECON, bool D3, bool CURV, bool GUARD, bool DETECT, bool LEAN, class TILE>
 ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CURV> &gx, const int k,
                        const Cell6 &qc, const bool stage_next, const Cell6 &qn, const Raw5 &hal_next,
-                       Flux8 &fx_lo, Flux8 &fy_lo, bool &flagged, const bool det FPROF_ARGS) {
+                       Flux8 &fx_lo, Flux8 &fy_lo, bool &flagged, const bool det, const bool qn_tiny FPROF_ARGS) {
   FPROF(0);
   constexpr bool PG = CURV && RECON == 1; // PLM_G instead of the uniform-mesh slope
   constexpr int SKIP = CURV ? 0 : ARTEMIS_FLAT_SKIP; // flat-wave guards: the Cartesian march only
-  constexpr bool SK1 = (SKIP == 1), SK6 = (SKIP == 2 && RECON == 1), SKF = (SKIP != 0);
+  constexpr bool SK3 = (SKIP == 3 && RECON == 1); // two levels: SK6's guard, then SK1's (ARTEMIS_FLAT_SKIP_INNER) or none
+  // ... whose verdicts the lean form combines with `&`, all of them formed first (`&&` evaluates lane by lane: a divergent
+  // branch per term); the full form keeps `&&` -- six verdicts at once cost its HLLE stage 2 twelve bytes of scratch
+  constexpr bool SKE = SK3 && LEAN;
+  constexpr bool SK1 = (SKIP == 1) || (SK3 && ARTEMIS_FLAT_SKIP_INNER != 0), SK6 = (SKIP == 2 && RECON == 1) || SK3, SKF = (SKIP != 0);
   bool fastp = true; // every division hand-scheduled (no tiny velocity in this plane's tile)
   // LDS ordering rule of this function (pattern 5): a store to S orders every later load of S
   // behind it -- the compiler cannot tell the members apart through run-time indices -- and a load that is used at
@@ -320,7 +339,7 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   }
   if constexpr (GUARD) flagged = (flag_ != 0), fastp = !flagged;
   double ux_[6], uy_[6]; // upper face values: stored after the last slope
-  // (FLAT: the direction's guard of ARTEMIS_FLAT_SKIP = 2 found the six slopes zero on every lane)
+  // (FLAT: the direction's guard of ARTEMIS_FLAT_SKIP = 2 / 3 found the six slopes zero on every lane)
 #define SLOPE(m, n, lm, rm, lov, upv, geo, FLAT)                                           \
   {                                                                                        \
     double up_, lo_;                                                                       \
@@ -337,10 +356,18 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
 #define FLAT6(lm, rm)                                                                      \
   (fastp && __all(plm_flat(lm[0], qc.d, rm[0]) && plm_flat(lm[1], qc.v1, rm[1]) && plm_flat(lm[2], qc.v2, rm[2]) && \
                   plm_flat(lm[3], qc.v3, rm[3]) && plm_flat(lm[4], qc.p, rm[4]) && (LEAN || plm_flat(lm[5], qc.e, rm[5]))))
+#define FLAT6E(lm, rm) /* SKE */                                                           \
+  (fastp && __all(plm_flat_i(lm[0], qc.d, rm[0]) & plm_flat_i(lm[1], qc.v1, rm[1]) & plm_flat_i(lm[2], qc.v2, rm[2]) & \
+                  plm_flat_i(lm[3], qc.v3, rm[3]) & plm_flat_i(lm[4], qc.p, rm[4])))
 #define SLX(m, n, F) SLOPE(m, n, xm_, xp_, lox, ux_, gx.g1, F)
 #define SLY(m, n, F) SLOPE(m, n, ym_, yp_, loy, uy_, gx.g2, F)
 #define SL6(S, F) S(d, 0, F) S(v1, 1, F) S(v2, 2, F) S(v3, 3, F) S(p, 4, F) if constexpr (!LEAN) S(e, 5, F)
-  if constexpr (SK6) {
+  if constexpr (SKE) {
+    if (FLAT6E(xm_, xp_)) { SL6(SLX, true) } else { SL6(SLX, false) }
+    if (multi_d) {
+      if (FLAT6E(ym_, yp_)) { SL6(SLY, true) } else { SL6(SLY, false) }
+    }
+  } else if constexpr (SK6) {
     if (FLAT6(xm_, xp_)) { SL6(SLX, true) } else { SL6(SLX, false) }
     if (multi_d) {
       if (FLAT6(ym_, yp_)) { SL6(SLY, true) } else { SL6(SLY, false) }
@@ -352,6 +379,7 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
 #undef SL6
 #undef SLX
 #undef SLY
+#undef FLAT6E
 #undef FLAT6
 #undef SLOPE
 #pragma unroll
@@ -370,19 +398,37 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   bool flat_ = false;                                                                      \
   if constexpr (SK6) {                                                                     \
     bool f_ = true;                                                                        \
-    _Pragma("unroll") for (int n = 0; n < NQ; ++n) f_ = f_ && plm_flat(pm_[n], pc_[n], pp_[n]); \
+    if constexpr (SKE) {                                                                   \
+      int fi_ = 1;                                                                         \
+      _Pragma("unroll") for (int n = 0; n < NQ; ++n) fi_ &= plm_flat_i(pm_[n], pc_[n], pp_[n]); \
+      f_ = (fi_ != 0);                                                                     \
+    } else {                                                                               \
+      _Pragma("unroll") for (int n = 0; n < NQ; ++n) f_ = f_ && plm_flat(pm_[n], pc_[n], pp_[n]); \
+    }                                                                                      \
     flat_ = fastp && __all(f_);                                                            \
   }                                                                                        \
-  _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                         \
-    double up_, lo_;                                                                       \
-    if constexpr (PG) {                                                                    \
-      if (fastp) plm_g_shared<2>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                   \
-      else plm_g_shared<0>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                         \
+  if constexpr (SK3) { /* two levels: the duty's flat side is straight-line code */       \
+    if (flat_) {                                                                           \
+      _Pragma("unroll") for (int n = 0; n < NQ; ++n)                                       \
+        po_[n] = side ? lo_val<RECON>(pc_[n], 0.0) : up_val<RECON>(pc_[n], 0.0);           \
     } else {                                                                               \
-      const double s_ = flat_ ? 0.0 : slope_sel<RECON, SK1>(pm_[n], pc_[n], pp_[n], fastp); \
-      lo_ = lo_val<RECON>(pc_[n], s_), up_ = up_val<RECON>(pc_[n], s_);                    \
+      _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                     \
+        const double s_ = slope_sel<RECON, SK1>(pm_[n], pc_[n], pp_[n], fastp);            \
+        po_[n] = side ? lo_val<RECON>(pc_[n], s_) : up_val<RECON>(pc_[n], s_);             \
+      }                                                                                    \
     }                                                                                      \
-    po_[n] = side ? lo_ : up_;                                                             \
+  } else {                                                                                 \
+    _Pragma("unroll") for (int n = 0; n < NQ; ++n) {                                       \
+      double up_, lo_;                                                                     \
+      if constexpr (PG) {                                                                  \
+        if (fastp) plm_g_shared<2>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                 \
+        else plm_g_shared<0>(pm_[n], pc_[n], pp_[n], up_, lo_, geo);                       \
+      } else {                                                                             \
+        const double s_ = flat_ ? 0.0 : slope_sel<RECON, SK1>(pm_[n], pc_[n], pp_[n], fastp); \
+        lo_ = lo_val<RECON>(pc_[n], s_), up_ = up_val<RECON>(pc_[n], s_);                  \
+      }                                                                                    \
+      po_[n] = side ? lo_ : up_;                                                           \
+    }                                                                                      \
   }
   if (t >= 128 && t < 128 + 2 * FTY) { // cells i0-1 (upper value) and i0+32 (lower value)
     const int u = t - 128, row = u >> 1, side = u & 1;
@@ -394,8 +440,12 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
     DUTY_SLOPES(S.GX1[side])
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-      if (side) S.LOX[n][row] = po_[n];
-      else S.UPX[n][row][0] = po_[n];
+      if constexpr (SK3) { // (one store to a selected address: the duty's two code paths kept the branch per value)
+        *(side ? &S.LOX[n][row] : &S.UPX[n][row][0]) = po_[n];
+      } else {
+        if (side) S.LOX[n][row] = po_[n];
+        else S.UPX[n][row][0] = po_[n];
+      }
     }
   }
   if (multi_d && t >= 192 && t < 256) { // rows j0-1 (upper value) and j0+8 (lower value)
@@ -408,8 +458,12 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
     DUTY_SLOPES(S.GX2[side][cx])
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-      if (side) S.LOY[n][cx] = po_[n];
-      else S.UPY[n][0][cx] = po_[n];
+      if constexpr (SK3) {
+        *(side ? &S.LOY[n][cx] : &S.UPY[n][0][cx]) = po_[n];
+      } else {
+        if (side) S.LOY[n][cx] = po_[n];
+        else S.UPY[n][0][cx] = po_[n];
+      }
     }
   }
 #undef DUTY_SLOPES
@@ -468,7 +522,11 @@ ADEV void plane_sweeps(TILE &S, const PackView &P, const Ctx &x, const GeoCtx<CU
   if (stage_next) {
     stage_plane<LEAN>(S, x, qn, hal_next);
     if constexpr (GUARD || DETECT) {
-      if (GUARD || det) stage_plane_flag(S, x, qn, hal_next, (k + 1) & 1);
+      if constexpr (DETECT && D3) { // (qn was tested as plane k + 2 of the own column one trip ago: the caller's ahead1)
+        if (det) stage_plane_flag_halo(S, x, qn_tiny, hal_next, (k + 1) & 1);
+      } else {
+        if (GUARD || det) stage_plane_flag(S, x, qn, hal_next, (k + 1) & 1);
+      }
     }
   }
   FPROF(3);
@@ -965,7 +1023,8 @@ STAGE_KERNEL_HEAD {
   // bit exact with them (the fused Cartesian stage does without: DESIGN.md section 4)
   constexpr bool GUARD = (CURV && RECON == 1) || FLUXES;
   constexpr int SKIP = CURV ? 0 : ARTEMIS_FLAT_SKIP; // flat-wave guards of the x3 sweep (plane_sweeps: x1, x2)
-  [[maybe_unused]] constexpr bool SK1 = (SKIP == 1), SK6 = (SKIP == 2 && RECON == 1), SKF = (SKIP != 0);
+  [[maybe_unused]] constexpr bool SK3 = (SKIP == 3 && RECON == 1), SKE = SK3 && LEAN; // (plane_sweeps)
+  [[maybe_unused]] constexpr bool SK1 = (SKIP == 1) || (SK3 && ARTEMIS_FLAT_SKIP_INNER != 0), SK6 = (SKIP == 2 && RECON == 1) || SK3, SKF = (SKIP != 0);
   // the Cartesian stage: detect-and-redo instead of a second code path (which costs registers it does not have)
 #ifndef ARTEMIS_DETECT
 #define ARTEMIS_DETECT 1
@@ -999,7 +1058,7 @@ STAGE_KERNEL_HEAD {
     }
     __syncthreads();
     bool flagged = false;
-    plane_sweeps<RIEMANN, RECON, false, CURV, GUARD, DETECT, LEAN>(S, P, x, gx, k0, qc, false, qc, hal, fx_lo, fy_lo, flagged, detect FPROF_PASS);
+    plane_sweeps<RIEMANN, RECON, false, CURV, GUARD, DETECT, LEAN>(S, P, x, gx, k0, qc, false, qc, hal, fx_lo, fy_lo, flagged, detect, false FPROF_PASS);
     if constexpr (CURV) {
       DFlux24 df{};
       if (gx.m3) gx.co.c3 = gx.m3[MT3_COS * (P.nk + 1) + k0], gx.co.s3 = gx.m3[MT3_SIN * (P.nk + 1) + k0];
@@ -1043,15 +1102,31 @@ STAGE_KERNEL_HEAD {
       } else {
         const bool f0 = !(FLUXES && __any(tiny_v(qmm) || tiny_v(qc) || tiny_v(qn)));
         bool flat_ = false;
-        if constexpr (SK6) {
+        if constexpr (SKE) { // (verdicts first, combined with `&`: plane_sweeps)
+#define ZF0(m, n) &plm_flat_i(qmm.m, qc.m, qn.m)
+          flat_ = f0 && __all(1 FOR5(ZF0));
+#undef ZF0
+        } else if constexpr (SK6) {
 #define ZF0(m, n) &&plm_flat(qmm.m, qc.m, qn.m)
           flat_ = f0 && __all(true FOR5(ZF0) && (LEAN || (true ZF0(e, 5))));
 #undef ZF0
         }
 #define ZL0(m, n) zl.m = up_val<RECON>(qc.m, flat_ ? 0.0 : slope_sel<RECON, SK1>(qmm.m, qc.m, qn.m, f0));
-        FOR5(ZL0)
+#define ZL0F(m, n) zl.m = up_val<RECON>(qc.m, 0.0);
         if constexpr (LEAN) zl.e = 0.0;
-        else { ZL0(e, 5) }
+        if constexpr (SK3) { // two levels: the flat side is straight-line code
+          if (flat_) {
+            FOR5(ZL0F)
+            if constexpr (!LEAN) { ZL0F(e, 5) }
+          } else {
+            FOR5(ZL0)
+            if constexpr (!LEAN) { ZL0(e, 5) }
+          }
+        } else {
+          FOR5(ZL0)
+          if constexpr (!LEAN) { ZL0(e, 5) }
+        }
+#undef ZL0F
 #undef ZL0
       }
     }
@@ -1079,11 +1154,13 @@ STAGE_KERNEL_HEAD {
       Flux8 fx_lo, fy_lo;
       bool flagged = false;
       if (k >= k0) {
-        plane_sweeps<RIEMANN, RECON, true, CURV, GUARD, DETECT, LEAN>(S, P, x, gx, k, qc, k < k1, qn, hal, fx_lo, fy_lo, flagged, detect FPROF_PASS);
+        plane_sweeps<RIEMANN, RECON, true, CURV, GUARD, DETECT, LEAN>(S, P, x, gx, k, qc, k < k1, qn, hal, fx_lo, fy_lo, flagged, detect, ahead1 FPROF_PASS);
       } else { // priming trip: stage the first plane
         stage_plane<LEAN>(S, x, qn, hal);
-        if constexpr (GUARD || DETECT) {
-          if (GUARD || detect) stage_plane_flag(S, x, qn, hal, k0 & 1);
+        if constexpr (DETECT) { // (ahead1 == tiny_v(qn): set before the loop)
+          if (detect) stage_plane_flag_halo(S, x, ahead1, hal, k0 & 1);
+        } else if constexpr (GUARD) {
+          stage_plane_flag(S, x, qn, hal, k0 & 1);
         }
         __syncthreads();
       }
@@ -1129,7 +1206,11 @@ STAGE_KERNEL_HEAD {
   }
 #define ZSL6(F) ZSL(d, F) ZSL(v1, F) ZSL(v2, F) ZSL(v3, F) ZSL(p, F) if constexpr (!LEAN) ZSL(e, F)
         if constexpr (LEAN) zr.e = zl_next.e = 0.0;
-        if constexpr (SK6) {
+        if constexpr (SKE) {
+#define ZF(m, n) &plm_flat_i(qc.m, qn.m, qnn.m)
+          if (fast_col && __all(1 FOR5(ZF))) { ZSL6(true) } else { ZSL6(false) }
+#undef ZF
+        } else if constexpr (SK6) {
 #define ZF(m, n) &&plm_flat(qc.m, qn.m, qnn.m)
           if (fast_col && __all(true FOR5(ZF) && (LEAN || (true ZF(e, 5))))) { ZSL6(true) } else { ZSL6(false) }
 #undef ZF
