@@ -292,6 +292,56 @@ int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, in
   artemis::launch_pack_fields(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, out_dev, S(stream));
   return after_launch("pack_fields");
 }
+// the shifts of artemis_hip_pack_fields_level: "" and the element offset of every block (off[nblocks]: the total), or
+// what is wrong with the first block that breaks a rule
+static std::string level_offsets(const artemis_pack_t *p, int block0, int nblocks, int ncomp, const int *shift, std::vector<long> &off) {
+  off.assign(static_cast<size_t>(nblocks) + 1, 0);
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  for (int b = 0; b < nblocks; ++b) {
+    const int s = shift[b];
+    if (s > artemis::FIELDS_MAX_SHIFT || s < -artemis::FIELDS_MAX_SHIFT)
+      return "pack fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", |shift| <= 3 is built";
+    long zones = 1;
+    for (int d = 0; d < 3; ++d) {
+      if (s > 0 && nx[d] > 1 && nx[d] % (1 << s) != 0)
+        return "pack fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", and its nx" +
+               std::to_string(d + 1) + " = " + std::to_string(nx[d]) + " is not divisible by " + std::to_string(1 << s);
+      zones *= artemis::level_extent(nx[d], s);
+    }
+    off[static_cast<size_t>(b) + 1] = off[static_cast<size_t>(b)] + zones * ncomp;
+  }
+  return "";
+}
+size_t artemis_hip_pack_fields_level_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                           const int *shift_host) {
+  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return 0;
+  artemis::FieldSelection S;
+  if (*field_selection(p, nsel, sel, S)) return 0;
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0 || (nblocks > 0 && !shift_host)) return 0;
+  std::vector<long> off;
+  if (!level_offsets(p, block0, nblocks, S.ncomp, shift_host, off).empty()) return 0;
+  return static_cast<size_t>(off.back()) * (single ? sizeof(float) : sizeof(double));
+}
+int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                  const int *shift_host, void *out_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldSelection F;
+  const char *bad = field_selection(p, nsel, sel, F);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (nsel == 0) return fail(ARTEMIS_HIP_EINVAL, "pack fields level: no variables");
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
+    return fail(ARTEMIS_HIP_EINVAL, "pack fields level: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
+  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "pack fields level: the primitive tables of the fluids asked for are required");
+  if (nblocks == 0) return 0;
+  if (!shift_host) return fail(ARTEMIS_HIP_EINVAL, "pack fields level: null shift_host");
+  std::vector<long> off;
+  const std::string rule = level_offsets(p, block0, nblocks, F.ncomp, shift_host, off);
+  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
+  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "pack fields level: null out_dev");
+  artemis::launch_pack_fields_level(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, shift_host, off.data(), out_dev, S(stream));
+  return after_launch("pack_fields_level");
+}
 int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                               const void *in_dev, void *stream) {
   if (int rc = validate(p)) return rc;

@@ -42,6 +42,9 @@ extern "C" int artemis_hip_history_sums(const artemis_pack_t *p, double *sums_de
 // ... and so is the kernel of the field outputs: without it the gather forms the same expressions in a host loop
 extern "C" int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                        void *out_dev, void *stream) __attribute__((weak));
+// ... and the kernels that resample them to a refinement level: without them the same tree in a host loop
+extern "C" int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                             const int *shift_host, void *out_dev, void *stream) __attribute__((weak));
 // ... and its inverse, which artemis_sim_scatter_fields sets a state with: without it the same expressions in a host loop
 extern "C" int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                          const void *in_dev, void *stream) __attribute__((weak));
@@ -498,6 +501,15 @@ struct artemis_sim_impl {
   // most FIELDS_STAGE_MB (default 256) MiB, one block where a block is larger; allocated by the first gather
   DevBuf field_stage;
   size_t gather_fields(const std::vector<int> &codes, bool single, void *host_out);
+  void host_block_components(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, std::vector<Real> &vals,
+                             std::vector<Real> *vol);
+  // ... resampled to refinement level `level` (artemis_sim_gather_fields_level); offsets: nb + 1 element offsets or null
+  size_t gather_fields_level(const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets);
+  int finest_level() const { // the finest level this run's mesh can ever hold
+    int f = adaptive ? amr_max_level : 0;
+    for (const Region &r : regions) f = std::max(f, r.level);
+    return f;
+  }
   // artemis_sim_scatter_fields: the inverse, through the same staging buffer, then the sequence a problem generator ends with
   size_t scatter_fields(const std::vector<int> &codes, bool single, const void *host_in, double new_time);
   int errors(double *out);
@@ -3509,6 +3521,81 @@ int artemis_sim_impl::history_device(double *out) {
   return nout;
 }
 
+// The host form of put_zone (kernels_fields.hip): every component of `codes` of block b's interior zones as doubles,
+// vals[component][nk][nj][ni]; vol (optional): Coords::Volume of the same zones
+void artemis_sim_impl::host_block_components(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp,
+                                             std::vector<Real> &vals, std::vector<Real> *vol) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  const size_t zones = static_cast<size_t>(mbnx[0]) * mbnx[1] * mbnx[2];
+  vals.assign(static_cast<size_t>(ncomp) * zones, 0.0);
+  if (vol) vol->assign(zones, 0.0);
+  std::vector<Real> g, d;
+  if (nsg) g = download(gprim[base], b);
+  if (nsd) d = download(dprim[base], b);
+  for (int k = ks; k <= ke; ++k)
+    for (int j = js; j <= je; ++j)
+      for (int i = is; i <= ie; ++i) {
+        const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
+        const size_t z = (static_cast<size_t>(k - ks) * mbnx[1] + (j - js)) * mbnx[0] + (i - is);
+        auto put = [&](int comp, Real v) { vals[comp * zones + z] = v; };
+        if (vol) (*vol)[z] = cell_coords(b, k, j, i).volume();
+        Real hx[3] = {1.0, 1.0, 1.0}; // GetScaleFactors (geometry.hpp:384-388)
+        if (coords != ARTEMIS_CARTESIAN) {
+          const artemis::DCoords co = cell_coords(b, k, j, i);
+          hx[1] = co.hx2v(), hx[2] = co.hx3v();
+        }
+        for (int n = 0; n < nsg; ++n) { // prim_to_cons_kernel's expressions (kernels_unfused.hip; fill_derived.cpp:212-276)
+          Real w_d = g[n * N + c];
+          w_d = (w_d > dfloor_gas) ? w_d : dfloor_gas;
+          const Real vel[3] = {g[(nsg + 3 * n + 0) * N + c], g[(nsg + 3 * n + 1) * N + c], g[(nsg + 3 * n + 2) * N + c]};
+          Real w_s = g[(5 * nsg + n) * N + c];
+          w_s = (w_s > siefloor_gas) ? w_s : siefloor_gas;
+          const Real u_u = w_s * w_d;
+          const Real ke = 0.5 * w_d * (SQR(vel[0]) + SQR(vel[1]) + SQR(vel[2]));
+          for (size_t e = 0; e < codes.size(); ++e) {
+            const int at = comp0[e];
+            switch (codes[e]) {
+            case ARTEMIS_VAR_GAS_PRIM_DENSITY:
+            case ARTEMIS_VAR_GAS_CONS_DENSITY: put(at + n, w_d); break;
+            case ARTEMIS_VAR_GAS_PRIM_VELOCITY:
+              for (int q = 0; q < 3; ++q) put(at + 3 * n + q, vel[q]);
+              break;
+            case ARTEMIS_VAR_GAS_PRIM_PRESSURE: {
+              const Real pr = (gamma - 1.0) * w_d * w_s;
+              put(at + n, (0.0 < pr) ? pr : 0.0);
+            } break;
+            case ARTEMIS_VAR_GAS_PRIM_SIE: put(at + n, w_s); break;
+            case ARTEMIS_VAR_GAS_CONS_MOMENTUM:
+              for (int q = 0; q < 3; ++q) put(at + 3 * n + q, w_d * vel[q] * hx[q]);
+              break;
+            case ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY: put(at + n, u_u + ke); break;
+            case ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY: put(at + n, u_u); break;
+            default: break;
+            }
+          }
+        }
+        for (int m = 0; m < nsd; ++m) {
+          Real w_d = d[m * N + c];
+          w_d = (w_d > dfloor_dust) ? w_d : dfloor_dust;
+          const Real vel[3] = {d[(nsd + 3 * m + 0) * N + c], d[(nsd + 3 * m + 1) * N + c], d[(nsd + 3 * m + 2) * N + c]};
+          for (size_t e = 0; e < codes.size(); ++e) {
+            const int at = comp0[e];
+            switch (codes[e]) {
+            case ARTEMIS_VAR_DUST_PRIM_DENSITY:
+            case ARTEMIS_VAR_DUST_CONS_DENSITY: put(at + m, w_d); break;
+            case ARTEMIS_VAR_DUST_PRIM_VELOCITY:
+              for (int q = 0; q < 3; ++q) put(at + 3 * m + q, vel[q]);
+              break;
+            case ARTEMIS_VAR_DUST_CONS_MOMENTUM:
+              for (int q = 0; q < 3; ++q) put(at + 3 * m + q, w_d * vel[q] * hx[q]);
+              break;
+            default: break;
+            }
+          }
+        }
+      }
+}
+
 // Field output: the variables `codes` (enum artemis_field_var) of this rank's interior zones as [block][component][nk][nj]
 // [ni], double or float, formed from the primitives of the current buffer with PrimToCons's expressions: by
 // artemis_hip_pack_fields into a bounded staging buffer, one copy per block range (kernels_fields.hip), or -- a library
@@ -3541,77 +3628,129 @@ size_t artemis_sim_impl::gather_fields(const std::vector<int> &codes, bool singl
     }
     return static_cast<size_t>(nb) * block_bytes;
   }
+  std::vector<Real> q;
   for (int b = 0; b < nb; ++b) {
-    std::vector<Real> g, d;
-    if (nsg) g = download(gprim[base], b);
-    if (nsd) d = download(dprim[base], b);
+    host_block_components(b, codes, comp0, ncomp, q, nullptr);
     char *ob = static_cast<char *>(host_out) + static_cast<size_t>(b) * block_bytes;
-    for (int k = ks; k <= ke; ++k)
-      for (int j = js; j <= je; ++j)
-        for (int i = is; i <= ie; ++i) {
-          const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
-          const size_t z = (static_cast<size_t>(k - ks) * mbnx[1] + (j - js)) * mbnx[0] + (i - is);
-          auto put = [&](int comp, Real v) {
-            if (single) reinterpret_cast<float *>(ob)[comp * zones + z] = static_cast<float>(v);
-            else reinterpret_cast<double *>(ob)[comp * zones + z] = v;
-          };
-          Real hx[3] = {1.0, 1.0, 1.0}; // GetScaleFactors (geometry.hpp:384-388)
-          if (coords != ARTEMIS_CARTESIAN) {
-            const artemis::DCoords co = cell_coords(b, k, j, i);
-            hx[1] = co.hx2v(), hx[2] = co.hx3v();
-          }
-          for (int n = 0; n < nsg; ++n) { // prim_to_cons_kernel's expressions (kernels_unfused.hip; fill_derived.cpp:212-276)
-            Real w_d = g[n * N + c];
-            w_d = (w_d > dfloor_gas) ? w_d : dfloor_gas;
-            const Real vel[3] = {g[(nsg + 3 * n + 0) * N + c], g[(nsg + 3 * n + 1) * N + c], g[(nsg + 3 * n + 2) * N + c]};
-            Real w_s = g[(5 * nsg + n) * N + c];
-            w_s = (w_s > siefloor_gas) ? w_s : siefloor_gas;
-            const Real u_u = w_s * w_d;
-            const Real ke = 0.5 * w_d * (SQR(vel[0]) + SQR(vel[1]) + SQR(vel[2]));
-            for (size_t e = 0; e < codes.size(); ++e) {
-              const int at = comp0[e];
-              switch (codes[e]) {
-              case ARTEMIS_VAR_GAS_PRIM_DENSITY:
-              case ARTEMIS_VAR_GAS_CONS_DENSITY: put(at + n, w_d); break;
-              case ARTEMIS_VAR_GAS_PRIM_VELOCITY:
-                for (int q = 0; q < 3; ++q) put(at + 3 * n + q, vel[q]);
-                break;
-              case ARTEMIS_VAR_GAS_PRIM_PRESSURE: {
-                const Real pr = (gamma - 1.0) * w_d * w_s;
-                put(at + n, (0.0 < pr) ? pr : 0.0);
-              } break;
-              case ARTEMIS_VAR_GAS_PRIM_SIE: put(at + n, w_s); break;
-              case ARTEMIS_VAR_GAS_CONS_MOMENTUM:
-                for (int q = 0; q < 3; ++q) put(at + 3 * n + q, w_d * vel[q] * hx[q]);
-                break;
-              case ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY: put(at + n, u_u + ke); break;
-              case ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY: put(at + n, u_u); break;
-              default: break;
-              }
-            }
-          }
-          for (int m = 0; m < nsd; ++m) {
-            Real w_d = d[m * N + c];
-            w_d = (w_d > dfloor_dust) ? w_d : dfloor_dust;
-            const Real vel[3] = {d[(nsd + 3 * m + 0) * N + c], d[(nsd + 3 * m + 1) * N + c], d[(nsd + 3 * m + 2) * N + c]};
-            for (size_t e = 0; e < codes.size(); ++e) {
-              const int at = comp0[e];
-              switch (codes[e]) {
-              case ARTEMIS_VAR_DUST_PRIM_DENSITY:
-              case ARTEMIS_VAR_DUST_CONS_DENSITY: put(at + m, w_d); break;
-              case ARTEMIS_VAR_DUST_PRIM_VELOCITY:
-                for (int q = 0; q < 3; ++q) put(at + 3 * m + q, vel[q]);
-                break;
-              case ARTEMIS_VAR_DUST_CONS_MOMENTUM:
-                for (int q = 0; q < 3; ++q) put(at + 3 * m + q, w_d * vel[q] * hx[q]);
-                break;
-              default: break;
-              }
-            }
-          }
-        }
+    for (size_t e = 0; e < q.size(); ++e) {
+      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(q[e]);
+      else reinterpret_cast<double *>(ob)[e] = q[e];
+    }
   }
   return static_cast<size_t>(nb) * block_bytes;
+}
+
+// The same gather with every block resampled to the zone size of refinement level `level` (artemis_driver.h "field output
+// at a level"; artemis_hip.h has the definition): block b has shift s = its level - level and follows block b - 1 in
+// host_out as [component][nk'][nj'][ni'].  artemis_hip_pack_fields_level into the staging buffer, the block ranges cut by
+// BYTES (blocks differ in size), or -- a library without that kernel -- the same tree in a host loop over the downloaded
+// primitives.  Every shift is checked before anything is written.  offsets (nb + 1 longs, or null): the element offset of
+// every block and the total.  host_out = NULL: sizes only.  Returns the bytes.
+size_t artemis_sim_impl::gather_fields_level(const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  std::vector<int> comp0;
+  int ncomp = 0;
+  for (const int code : codes) {
+    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
+    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
+    comp0.push_back(ncomp), ncomp += n;
+  }
+  if (ncomp == 0) throw std::runtime_error("fields: no variables");
+  const size_t esz = single ? sizeof(float) : sizeof(double);
+  std::vector<int> shift(static_cast<size_t>(nb));
+  std::vector<long> off(static_cast<size_t>(nb) + 1, 0);
+  for (int b = 0; b < nb; ++b) {
+    const int s = blocks[b].level - level;
+    const std::string bad = artemis_out::level_rule(s, mbnx);
+    if (!bad.empty())
+      throw std::runtime_error("fields at level " + std::to_string(level) + ": local block " + std::to_string(b) + " (gid " + std::to_string(blocks[b].gid) +
+                               ") on level " + std::to_string(blocks[b].level) + " " + bad);
+    shift[b] = s;
+    long zones = 1;
+    for (int d = 0; d < 3; ++d) zones *= artemis_out::level_extent(mbnx[d], s);
+    off[b + 1] = off[b] + zones * ncomp;
+  }
+  if (offsets) std::copy(off.begin(), off.end(), offsets);
+  const size_t total = static_cast<size_t>(off[nb]) * esz;
+  if (!host_out || total == 0) return total;
+  if (artemis_hip_pack_fields_level) {
+    const artemis_pack_t p = make_pack(base);
+    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
+    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
+    for (int b0 = 0; b0 < nb;) {
+      int n = 1; // as many blocks as the cap holds, one where a block is larger
+      while (b0 + n < nb && static_cast<size_t>(off[b0 + n + 1] - off[b0]) * esz <= cap) ++n;
+      const size_t bytes = static_cast<size_t>(off[b0 + n] - off[b0]) * esz;
+      const size_t need = (bytes + sizeof(double) - 1) / sizeof(double);
+      if (field_stage.n < need) field_stage.alloc(need);
+      CK(artemis_hip_pack_fields_level(&p, b0, n, static_cast<int>(codes.size()), codes.data(), single ? 1 : 0, shift.data() + b0, field_stage.p, stream),
+         "pack fields level");
+      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(off[b0]) * esz, field_stage.p, bytes, stream), "d2h");
+      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffer)
+      b0 += n;
+    }
+    return total;
+  }
+  std::vector<Real> q, vol, cur, nxt;
+  for (int b = 0; b < nb; ++b) {
+    const int s = shift[b];
+    host_block_components(b, codes, comp0, ncomp, q, &vol);
+    int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
+    const size_t zin = vol.size();
+    std::vector<Real> res; // [ncomp][nk'][nj'][ni']
+    if (s > 0) {
+      // rows 0 .. ncomp - 1: N = V q, row ncomp: V; each goes s times up the tree of restriction.hpp:107-112
+      cur.assign((static_cast<size_t>(ncomp) + 1) * zin, 0.0);
+      for (int c = 0; c < ncomp; ++c)
+        for (size_t z = 0; z < zin; ++z) cur[c * zin + z] = vol[z] * q[c * zin + z];
+      std::copy(vol.begin(), vol.end(), cur.begin() + static_cast<size_t>(ncomp) * zin);
+      for (int m = 0; m < s; ++m) {
+        const bool a[3] = {n[0] > 1, n[1] > 1, n[2] > 1};
+        const int o[3] = {a[0] ? n[0] / 2 : 1, a[1] ? n[1] / 2 : 1, a[2] ? n[2] / 2 : 1};
+        const size_t zi = static_cast<size_t>(n[0]) * n[1] * n[2], zo = static_cast<size_t>(o[0]) * o[1] * o[2];
+        nxt.assign((static_cast<size_t>(ncomp) + 1) * zo, 0.0);
+        for (int c = 0; c <= ncomp; ++c) {
+          const Real *x = cur.data() + c * zi;
+          auto child = [&](int K, int J, int I, int ok, int oj, int oi) -> Real { // 0.0: the offset-1 child of an inactive direction
+            if ((ok && !a[2]) || (oj && !a[1]) || (oi && !a[0])) return 0.0;
+            const int k = a[2] ? 2 * K + ok : K, j = a[1] ? 2 * J + oj : J, i = a[0] ? 2 * I + oi : I;
+            return x[(static_cast<size_t>(k) * n[1] + j) * n[0] + i];
+          };
+          for (int K = 0; K < o[2]; ++K)
+            for (int J = 0; J < o[1]; ++J)
+              for (int I = 0; I < o[0]; ++I)
+                nxt[c * zo + (static_cast<size_t>(K) * o[1] + J) * o[0] + I] =
+                    ((child(K, J, I, 0, 0, 0) + child(K, J, I, 0, 1, 0)) + (child(K, J, I, 0, 0, 1) + child(K, J, I, 0, 1, 1))) +
+                    ((child(K, J, I, 1, 0, 0) + child(K, J, I, 1, 1, 0)) + (child(K, J, I, 1, 0, 1) + child(K, J, I, 1, 1, 1)));
+        }
+        cur.swap(nxt);
+        for (int d = 0; d < 3; ++d) n[d] = o[d];
+      }
+      const size_t zo = static_cast<size_t>(n[0]) * n[1] * n[2];
+      res.resize(static_cast<size_t>(ncomp) * zo);
+      for (int c = 0; c < ncomp; ++c)
+        for (size_t z = 0; z < zo; ++z) res[c * zo + z] = cur[c * zo + z] / cur[static_cast<size_t>(ncomp) * zo + z];
+    } else {
+      const int r = -s;
+      const int rs[3] = {n[0] > 1 ? r : 0, n[1] > 1 ? r : 0, n[2] > 1 ? r : 0};
+      const int o[3] = {n[0] << rs[0], n[1] << rs[1], n[2] << rs[2]};
+      const size_t zo = static_cast<size_t>(o[0]) * o[1] * o[2];
+      res.resize(static_cast<size_t>(ncomp) * zo);
+      for (int c = 0; c < ncomp; ++c)
+        for (int k = 0; k < o[2]; ++k)
+          for (int j = 0; j < o[1]; ++j)
+            for (int i = 0; i < o[0]; ++i)
+              res[c * zo + (static_cast<size_t>(k) * o[1] + j) * o[0] + i] =
+                  q[c * zin + (static_cast<size_t>(k >> rs[2]) * n[1] + (j >> rs[1])) * n[0] + (i >> rs[0])];
+    }
+    if (static_cast<long>(res.size()) != off[b + 1] - off[b]) throw std::runtime_error("fields at a level: size mismatch");
+    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(off[b]) * esz;
+    for (size_t e = 0; e < res.size(); ++e) {
+      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(res[e]);
+      else reinterpret_cast<double *>(ob)[e] = res[e];
+    }
+  }
+  return total;
 }
 
 // The inverse of gather_fields: `host_in` holds one complete form of the state per fluid (fields_form.hpp) for this rank's
@@ -4158,6 +4297,8 @@ Clock clock_of(const artemis_sim_t *sim) {
   Clock c;
   c.time = S.time, c.dt = S.dt, c.tlim = S.tlim, c.ncycle = S.ncycle, c.nlim = S.nlim, c.nblocks_global = S.nblocks_global;
   c.ns_gas = S.do_gas ? S.ns_gas : 0, c.ns_dust = S.do_dust ? S.ns_dust : 0, c.rank = S.rank;
+  c.finest_level = S.finest_level();
+  for (int d = 0; d < 3; ++d) c.mbnx[d] = S.mbnx[d];
   return c;
 }
 const std::string &deck_of(const artemis_sim_t *sim) { return sim->deck; }
@@ -4170,6 +4311,9 @@ size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool sin
 }
 size_t scatter_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, const void *host_in, double time) {
   return sim->p->scatter_fields(codes, single, host_in, time);
+}
+size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets) {
+  return sim->p->gather_fields_level(codes, single, level, host_out, offsets);
 }
 FieldsLayout fields_layout(artemis_sim_t *sim) {
   const artemis_sim_impl &S = *sim->p;
@@ -4472,6 +4616,31 @@ long artemis_sim_gather_fields(artemis_sim_t *s, int nvar, const char *const *na
       ncomp += n;
     }
     const size_t bytes = s->p->gather_fields(codes, single != 0, host_out);
+    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
+  };
+  GUARD(gather(), return -1)
+  return ret;
+}
+long artemis_sim_gather_fields_level(artemis_sim_t *s, int nvar, const char *const *names, int single, int level, void *host_out,
+                                     long *block_offsets) {
+  long ret = -1;
+  if (!s->dead.empty()) {
+    g_sim_err = s->dead;
+    return -1;
+  }
+  auto gather = [&]() {
+    const artemis_out::Clock c = artemis_out::clock_of(s);
+    std::vector<int> codes;
+    int ncomp = 0;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = artemis_out::field_var_code(name);
+      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
+      if (n == 0) throw std::runtime_error("gather_fields_level: unknown variable " + name);
+      codes.push_back(code);
+      ncomp += n;
+    }
+    const size_t bytes = s->p->gather_fields_level(codes, single != 0, level, host_out, block_offsets);
     ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
   };
   GUARD(gather(), return -1)

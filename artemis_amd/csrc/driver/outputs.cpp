@@ -44,6 +44,8 @@ struct OutBlock {
   std::vector<std::string> variables;
   std::vector<int> codes;
   bool single = false, is_fld = false;
+  bool has_level = false; // fld: `level = L`, every block resampled to the zone size of refinement level L (may be negative)
+  int level = 0;
   std::string skip;
 };
 
@@ -114,6 +116,14 @@ void parse_fld(artemis_host::ParameterInput &pin, const Clock &c, OutBlock &b) {
     } else b.codes.push_back(code);
   }
   if (b.skip.empty() && pin.GetOrAddBoolean(b.name, "ghost_zones", false)) b.skip = "ghost_zones is not built";
+  if (pin.DoesParameterExist(b.name, "level")) {
+    b.has_level = true, b.level = pin.GetInteger(b.name, "level");
+    // the worst shifts this deck can ever produce: its finest possible level and the root grid
+    for (const int lv : {c.finest_level, 0}) {
+      const std::string rule = level_rule(lv - b.level, c.mbnx);
+      if (b.skip.empty() && !rule.empty()) b.skip = "level " + std::to_string(b.level) + ": a block on level " + std::to_string(lv) + " " + rule;
+    }
+  }
   if (!b.skip.empty()) b.kind = SKIPPED;
 }
 
@@ -233,8 +243,11 @@ void write_file(const std::string &name, const void *data, size_t bytes) {
   if (std::fclose(f) != 0 || bad) throw std::runtime_error("writing " + name + " failed");
 }
 
-std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single) {
-  std::string j = "{\"format\": \"artemis_fld\", \"version\": 1, \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
+// level = null: version 1.  Else version 2: "level", and every block entry carries the nx it was written with and the
+// element offset of its first value in its rank's part (the blocks of a rank follow each other in index order).
+std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single, const int *level) {
+  std::string j = std::string("{\"format\": \"artemis_fld\", \"version\": ") + (level ? "2, \"level\": " + std::to_string(*level) : std::string("1")) +
+                  ", \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
                   ", \"cycle\": " + std::to_string(c.ncycle) + ", \"coordinates\": " + json_str(L.coordinates) +
                   ", \"ndim\": " + std::to_string(L.ndim) + ", \"nghost\": 0, \"dtype\": " + (single ? "\"<f4\"" : "\"<f8\"") +
                   ", \"gamma\": " + json_num(L.gamma) + ", \"ns_gas\": " + std::to_string(c.ns_gas) + ", \"ns_dust\": " + std::to_string(c.ns_dust) +
@@ -252,8 +265,33 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
     j += "]}";
   }
   j += "],\n \"blocks\": [";
+  int ncomp = 0;
+  for (const int code : codes) ncomp += field_var_components(code, c.ns_gas, c.ns_dust);
+  std::vector<long> offset(L.blocks.size(), 0); // version 2
+  if (level) {
+    std::vector<std::vector<size_t>> of_rank(static_cast<size_t>(L.nranks));
+    for (size_t g = 0; g < L.blocks.size(); ++g) of_rank[static_cast<size_t>(L.blocks[g].rank)].push_back(g);
+    for (std::vector<size_t> &gs : of_rank) {
+      std::sort(gs.begin(), gs.end(), [&](size_t a, size_t b) { return L.blocks[a].index < L.blocks[b].index; });
+      long at = 0;
+      for (const size_t g : gs) {
+        offset[g] = at;
+        const int s = L.blocks[g].level - *level;
+        at += static_cast<long>(ncomp) * level_extent(L.nx[0], s) * level_extent(L.nx[1], s) * level_extent(L.nx[2], s);
+      }
+    }
+  }
   for (size_t g = 0; g < L.blocks.size(); ++g) {
     const FieldBlock &B = L.blocks[g];
+    if (level) {
+      const int s = B.level - *level;
+      j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
+      for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
+      j += "], \"nx\": [" + std::to_string(level_extent(L.nx[0], s)) + ", " + std::to_string(level_extent(L.nx[1], s)) + ", " +
+           std::to_string(level_extent(L.nx[2], s)) + "], \"offset\": " + std::to_string(offset[g]) + ", \"rank\": " + std::to_string(B.rank) +
+           ", \"index\": " + std::to_string(B.index) + "}";
+      continue;
+    }
     j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
     for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
     j += "], \"nx\": " + nx + ", \"rank\": " + std::to_string(B.rank) + ", \"index\": " + std::to_string(B.index) + "}";
@@ -263,7 +301,7 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
 
 // One field dump (artemis_driver.h: artemis_sim_write_fields).  Every rank takes every vote, whatever happened to it
 // before: the votes are collective.
-void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single) {
+void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single, const int *level = nullptr) {
   std::string err, dir = path_in, tmp;
   while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
   tmp = dir + ".tmp";
@@ -284,8 +322,9 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   bool failed = vote(sim, !err.empty());
   if (!failed) {
     try {
-      std::vector<char> host(gather_fields(sim, codes, single, nullptr));
-      gather_fields(sim, codes, single, host.data());
+      std::vector<char> host(level ? gather_fields_level(sim, codes, single, *level, nullptr, nullptr) : gather_fields(sim, codes, single, nullptr));
+      if (level) gather_fields_level(sim, codes, single, *level, host.data(), nullptr);
+      else gather_fields(sim, codes, single, host.data());
       write_file(tmp + "/rank" + std::to_string(c.rank) + ".bin", host.data(), host.size());
     } catch (const std::exception &e) {
       err = e.what();
@@ -295,7 +334,7 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   if (!failed) {
     try {
       if (c.rank == 0) {
-        const std::string meta = meta_json(c, L, codes, single);
+        const std::string meta = meta_json(c, L, codes, single, level);
         write_file(tmp + "/meta.json", meta.data(), meta.size()); // last: a directory with it has all its parts
         remove_field_dir(dir);
         if (std::rename(tmp.c_str(), dir.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + dir + ": " + std::strerror(errno));
@@ -319,7 +358,7 @@ void write_field_dump(artemis_sim_t *sim, State &st, OutBlock &b, bool final) {
   char num[16];
   std::snprintf(num, sizeof num, "%05ld", b.counter);
   b.path = st.dir + "/" + st.problem_id + ".out" + std::to_string(b.index) + "." + (final ? std::string("final") : std::string(num)) + ".fld";
-  write_fields(sim, b.path, b.codes, b.single);
+  write_fields(sim, b.path, b.codes, b.single, b.has_level ? &b.level : nullptr);
   if (!final) b.counter++;
 }
 
@@ -427,6 +466,26 @@ int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, con
   }
 }
 
+int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int level) {
+  using namespace artemis_out;
+  try {
+    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
+    const Clock c = clock_of(sim);
+    std::vector<int> codes;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = field_var_code(name);
+      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
+      codes.push_back(code);
+    }
+    write_fields(sim, path, codes, single != 0, &level);
+    return 0;
+  } catch (const std::exception &e) {
+    artemis_ckpt::set_error(e.what());
+    return 1;
+  }
+}
+
 long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in, double time) {
   using namespace artemis_out;
   try {
@@ -471,6 +530,7 @@ int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long 
         j += ", \"variables\": [";
         for (size_t v = 0; v < b.variables.size(); ++v) j += (v ? ", " : "") + json_str(b.variables[v]);
         j += std::string("], \"single_precision\": ") + (b.single ? "true" : "false");
+        if (b.has_level) j += ", \"level\": " + std::to_string(b.level);
       }
       j += "}";
     }

@@ -15,6 +15,7 @@ struct Clock { // the driver's clock after a cycle and what a history row record
   double time = 0.0, dt = 0.0, tlim = -1.0;
   long ncycle = 0, nlim = -1, nblocks_global = 0;
   int ns_gas = 0, ns_dust = 0, rank = 0;
+  int finest_level = 0, mbnx[3] = {1, 1, 1}; // the finest level the mesh can ever hold; zones of a block
 };
 
 // ---- driver.cpp ------------------------------------------------------------------------------------------------------
@@ -66,6 +67,23 @@ FieldsLayout fields_layout(artemis_sim_t *sim);
 // artemis_hip_pack_fields and a bounded staging buffer, or -- a library without that kernel -- a host loop over the
 // downloaded primitives.  host_out = NULL: nothing is gathered.  Returns the bytes of the gather.
 size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out);
+// ---- ... at a refinement level: a block on level l asked for level L has shift s = l - L; s >= 1 restricts it s times
+// (volume-weighted), s <= -1 replicates its zones, along the ACTIVE directions (more than one zone) only
+constexpr int kMaxShift = 3;
+inline int level_extent(int n, int shift) { return n == 1 ? 1 : (shift >= 0 ? n >> shift : n << -shift); }
+// "" or the rule a block of nx zones breaks at this shift
+inline std::string level_rule(int shift, const int nx[3]) {
+  if (shift > kMaxShift || shift < -kMaxShift) return "would need shift " + std::to_string(shift) + ", |shift| <= 3 is built";
+  for (int d = 0; d < 3; ++d)
+    if (shift > 0 && nx[d] > 1 && nx[d] % (1 << shift) != 0)
+      return "would need shift " + std::to_string(shift) + ", and its nx" + std::to_string(d + 1) + " = " + std::to_string(nx[d]) +
+             " is not divisible by " + std::to_string(1 << shift);
+  return "";
+}
+// (driver.cpp) the gather with every block on the zone size of `level`, the blocks one after the other, each
+// [component][nk'][nj'][ni']; offsets (nblocks_local + 1 longs, or null): element offset of every block and the total.
+// host_out = NULL: sizes only.  Throws, before anything is written, for a block whose shift breaks a rule.
+size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets);
 // (driver.cpp) the inverse: host_in in that layout, holding one complete form of the state per fluid (csrc/fields_form.hpp),
 // becomes the interior primitives of the current buffer -- artemis_hip_unpack_fields out of the same staging buffer, or the
 // host loop -- and the state is completed as a problem generator's is; time = NaN keeps the clock, dt is estimated afresh.

@@ -128,6 +128,12 @@ struct FieldSelection {
   int code[FIELDS_MAX_SEL], comp0[FIELDS_MAX_SEL];
 };
 void launch_pack_fields(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, void *out, hipStream_t s);
+// ... at a chosen refinement level: block block0 + b is restricted shift[b] times (volume-weighted, shift > 0) or replicated
+// (shift < 0) and starts off[b] elements into `out`.  An extent of one zone is inactive: never halved or doubled.
+constexpr int FIELDS_MAX_SHIFT = 3;
+inline int level_extent(int n, int shift) { return n == 1 ? 1 : (shift >= 0 ? n >> shift : n << -shift); }
+void launch_pack_fields_level(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, const int *shift,
+                              const long *off, void *out, hipStream_t s);
 // ... and its inverse: the form of each fluid that the buffer holds (fields_form.hpp) written to the interior primitives
 void launch_unpack_fields(const PackView &P, int block0, int nblocks, const FieldUnpack &U, bool single, const void *in, hipStream_t s);
 } // namespace artemis

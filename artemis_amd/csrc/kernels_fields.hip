@@ -34,10 +34,95 @@ __device__ __forceinline__ void put(OUT *out, long at, double v) {
   out[at] = static_cast<OUT>(v); // (double -> float: round to nearest even, the correctly rounded narrowing)
 }
 
+// One zone of one species as PrimToCons sees it, and the components of a variable formed from it: the expressions every
+// kernel of this file that forms output values shares (f(width, d, v): component d of a variable of `width` components a
+// species).
+struct GasZone {
+  double w_d, vel1, vel2, vel3, w_s, u_u, ke;
+};
+struct DustZone {
+  double w_d, vel1, vel2, vel3;
+};
+__device__ __forceinline__ GasZone load_gas(const PackView &P, int b, int n, long c) {
+  const FluidView &f = P.gas;
+  const int nsg = f.ns, nv = 6 * nsg;
+  GasZone z;
+  z.w_d = f.prim[b * nv + n][c];
+  z.w_d = (z.w_d > f.dfloor) ? z.w_d : f.dfloor;
+  z.vel1 = f.prim[b * nv + nsg + 3 * n + 0][c];
+  z.vel2 = f.prim[b * nv + nsg + 3 * n + 1][c];
+  z.vel3 = f.prim[b * nv + nsg + 3 * n + 2][c];
+  z.w_s = f.prim[b * nv + 5 * nsg + n][c];
+  z.w_s = (z.w_s > f.siefloor) ? z.w_s : f.siefloor;
+  z.u_u = z.w_s * z.w_d;
+  z.ke = 0.5 * z.w_d * (sqr(z.vel1) + sqr(z.vel2) + sqr(z.vel3));
+  return z;
+}
+__device__ __forceinline__ DustZone load_dust(const PackView &P, int b, int m, long c) {
+  const FluidView &f = P.dust;
+  const int nsd = f.ns, nv = 4 * nsd;
+  DustZone z;
+  z.w_d = f.prim[b * nv + m][c];
+  z.w_d = (z.w_d > f.dfloor) ? z.w_d : f.dfloor;
+  z.vel1 = f.prim[b * nv + nsd + 3 * m + 0][c];
+  z.vel2 = f.prim[b * nv + nsd + 3 * m + 1][c];
+  z.vel3 = f.prim[b * nv + nsd + 3 * m + 2][c];
+  return z;
+}
+template <class F>
+__device__ __forceinline__ void gas_components(const GasZone &z, double gm1, const double hx[3], int code, F &&f) {
+  switch (code) {
+  case ARTEMIS_VAR_GAS_PRIM_DENSITY:
+  case ARTEMIS_VAR_GAS_CONS_DENSITY: f(1, 0, z.w_d); break;
+  case ARTEMIS_VAR_GAS_PRIM_VELOCITY: f(3, 0, z.vel1), f(3, 1, z.vel2), f(3, 2, z.vel3); break;
+  case ARTEMIS_VAR_GAS_PRIM_PRESSURE: f(1, 0, amax(0.0, gm1 * z.w_d * z.w_s)); break;
+  case ARTEMIS_VAR_GAS_PRIM_SIE: f(1, 0, z.w_s); break;
+  case ARTEMIS_VAR_GAS_CONS_MOMENTUM:
+    f(3, 0, z.w_d * z.vel1 * hx[0]), f(3, 1, z.w_d * z.vel2 * hx[1]), f(3, 2, z.w_d * z.vel3 * hx[2]);
+    break;
+  case ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY: f(1, 0, z.u_u + z.ke); break;
+  case ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY: f(1, 0, z.u_u); break;
+  default: break;
+  }
+}
+template <class F>
+__device__ __forceinline__ void dust_components(const DustZone &z, const double hx[3], int code, F &&f) {
+  switch (code) {
+  case ARTEMIS_VAR_DUST_PRIM_DENSITY:
+  case ARTEMIS_VAR_DUST_CONS_DENSITY: f(1, 0, z.w_d); break;
+  case ARTEMIS_VAR_DUST_PRIM_VELOCITY: f(3, 0, z.vel1), f(3, 1, z.vel2), f(3, 2, z.vel3); break;
+  case ARTEMIS_VAR_DUST_CONS_MOMENTUM:
+    f(3, 0, z.w_d * z.vel1 * hx[0]), f(3, 1, z.w_d * z.vel2 * hx[1]), f(3, 2, z.w_d * z.vel3 * hx[2]);
+    break;
+  default: break;
+  }
+}
+
+// every requested component of zone (k, j, i) of block b, component c at o[c * zones]
+template <bool CURV, class OUT>
+__device__ __forceinline__ void put_zone(const PackView &P, const FieldSelection &S, int b, int k, int j, int i, OUT *o, long zones) {
+  const long c = (static_cast<long>(k) * P.nj + j) * P.ni + i;
+  double hx[3];
+  scale_factors<CURV>(P, b, k, j, i, hx);
+  for (int n = 0; n < (S.want_gas ? P.gas.ns : 0); ++n) {
+    const GasZone g = load_gas(P, b, n, c);
+    for (int e = 0; e < S.nsel; ++e) {
+      const long at = S.comp0[e] * zones;
+      gas_components(g, P.gm1, hx, S.code[e], [&](int w, int d, double v) { put(o, at + (w * n + d) * zones, v); });
+    }
+  }
+  for (int m = 0; m < (S.want_dust ? P.dust.ns : 0); ++m) {
+    const DustZone g = load_dust(P, b, m, c);
+    for (int e = 0; e < S.nsel; ++e) {
+      const long at = S.comp0[e] * zones;
+      dust_components(g, hx, S.code[e], [&](int w, int d, double v) { put(o, at + (w * m + d) * zones, v); });
+    }
+  }
+}
+
 template <bool CURV, class OUT>
 __global__ __launch_bounds__(FTX *FTY) void pack_fields_kernel(const PackView P, const FieldTiles T, const FieldSelection S,
                                                               int block0, OUT *out) {
-  const int nsg = P.gas.ns, nsd = P.dust.ns;
   const int nx1 = P.ie - P.is + 1, nx2 = P.je - P.js + 1;
   const long zones = static_cast<long>(nx1) * nx2 * T.nkr; // interior zones of one block = stride of a component
   for (long tile = blockIdx.x; tile < T.ntile; tile += gridDim.x) {
@@ -48,69 +133,192 @@ __global__ __launch_bounds__(FTX *FTY) void pack_fields_kernel(const PackView P,
     const int b = block0 + lb;
     const int k = P.ks + static_cast<int>(bz % T.nkr);
     if (i > P.ie || j > P.je) continue;
-    const long c = (static_cast<long>(k) * P.nj + j) * P.ni + i;
     const long z = (static_cast<long>(k - P.ks) * nx2 + (j - P.js)) * nx1 + (i - P.is);
-    OUT *o = out + static_cast<long>(lb) * S.ncomp * zones + z;
-    double hx[3];
-    scale_factors<CURV>(P, b, k, j, i, hx);
-    for (int n = 0; n < (S.want_gas ? nsg : 0); ++n) {
-      const FluidView &f = P.gas;
-      const int nv = 6 * nsg;
-      double w_d = f.prim[b * nv + n][c];
-      w_d = (w_d > f.dfloor) ? w_d : f.dfloor;
-      const double vel1 = f.prim[b * nv + nsg + 3 * n + 0][c];
-      const double vel2 = f.prim[b * nv + nsg + 3 * n + 1][c];
-      const double vel3 = f.prim[b * nv + nsg + 3 * n + 2][c];
-      double w_s = f.prim[b * nv + 5 * nsg + n][c];
-      w_s = (w_s > f.siefloor) ? w_s : f.siefloor;
-      const double u_u = w_s * w_d;
-      const double ke = 0.5 * w_d * (sqr(vel1) + sqr(vel2) + sqr(vel3));
-      for (int e = 0; e < S.nsel; ++e) {
-        const long at = S.comp0[e] * zones;
-        switch (S.code[e]) {
-        case ARTEMIS_VAR_GAS_PRIM_DENSITY:
-        case ARTEMIS_VAR_GAS_CONS_DENSITY: put(o, at + n * zones, w_d); break;
-        case ARTEMIS_VAR_GAS_PRIM_VELOCITY:
-          put(o, at + (3 * n + 0) * zones, vel1), put(o, at + (3 * n + 1) * zones, vel2), put(o, at + (3 * n + 2) * zones, vel3);
-          break;
-        case ARTEMIS_VAR_GAS_PRIM_PRESSURE: put(o, at + n * zones, amax(0.0, P.gm1 * w_d * w_s)); break;
-        case ARTEMIS_VAR_GAS_PRIM_SIE: put(o, at + n * zones, w_s); break;
-        case ARTEMIS_VAR_GAS_CONS_MOMENTUM:
-          put(o, at + (3 * n + 0) * zones, w_d * vel1 * hx[0]);
-          put(o, at + (3 * n + 1) * zones, w_d * vel2 * hx[1]);
-          put(o, at + (3 * n + 2) * zones, w_d * vel3 * hx[2]);
-          break;
-        case ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY: put(o, at + n * zones, u_u + ke); break;
-        case ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY: put(o, at + n * zones, u_u); break;
-        default: break;
+    put_zone<CURV>(P, S, b, k, j, i, out + static_cast<long>(lb) * S.ncomp * zones + z, zones);
+  }
+}
+
+// ---- field output at a chosen refinement level (artemis_hip_pack_fields_level) ---------------------------------------
+// Every block of a launch has one shift s = its level - the level asked for.
+//
+// s >= 1, pack_fields_level_kernel<CURV, OUT, S>: the volume-weighted mean of RestrictAverage<GEOM> (restriction.hpp:
+// 42-114), applied S times with summed volumes.  Per input zone N = V q (q as put_zone forms it, V = Coords::Volume of
+// make_coords, Cartesian packs included) and V; both go up the reference's tree
+//   X(K,J,I) = ((c000 + c010) + (c001 + c011)) + ((c100 + c110) + (c101 + c111)),   c[ok][oj][oi] = X'(2K+ok, 2J+oj, 2I+oi)
+// S times (an inactive direction -- one zone -- is not halved and its offset-1 children are the literal 0.0, added as the
+// reference adds them), the output is N / V: one division, then the narrowing.  The read side is pack_fields_kernel's:
+// lanes along x1 over the INPUT zones, 64 to a wave, 8-byte loads, the primitives of a species read once per zone.  A
+// thread owns one output row and plane: it walks the 2^S rows and 2^S planes under them itself, in the order of the tree
+// (t counts the leaves; its bits are j0 k0 j1 k1 ...), and keeps one pending sum per direction and level, so
+//   the j pair     is two of its own values,
+//   the i pair     one exchange with lane ^ (1 << m) -- a + b and b + a are the same bits, both lanes hold the sum,
+//   the k pair     again its own.
+// Groups of 2^S lanes start at the interior's first zone (64 is a multiple of 8 and nx1 of 2^S: a tile's ragged tail is
+// whole groups); lanes past the row's end load its last zone and store nothing, rows past the block's end are whole waves
+// (blockDim.x is the wave).  So every lane of a wave takes every exchange.  No LDS, no atomics, vector stores by the lane
+// with (i - is) % 2^S == 0, 64-bit offsets.  All slots of a species are carried (11 + V of a gas species, 7 + V of a
+// dust species) and the ones asked for are divided and stored: the slots are registers only while their index is static.
+//
+// s <= 0, pack_fields_replicate_kernel: out(k, j, i) = q(k >> |s|, j >> |s|, i >> |s|) along the active directions, lanes
+// along the OUTPUT x1 -- exact copies, no slopes (a dump invents no gradients, and the ghost zones a prolongation reads
+// may be stale).
+constexpr int LEVEL_MAX_BLOCKS = 96;
+struct LevelBlocks {          // the blocks of one launch, by value: a dump is a handful of launches, no table to upload
+  int n, lb[LEVEL_MAX_BLOCKS]; // block of the range
+  long off[LEVEL_MAX_BLOCKS];  // element offset of its first value in the output
+};
+struct LevelTiles {
+  int gx, gy, nxo, nyo, nzo; // tiles along x1 (input zones: restrict; output zones: replicate) and along the output rows
+  long ntile;
+};
+static_assert(sizeof(PackView) + sizeof(FieldSelection) + sizeof(LevelBlocks) + sizeof(LevelTiles) + 64 <= 4096, "kernel arguments");
+
+template <int M>
+__device__ __forceinline__ double pair_lane(double v) { // v of lane ^ (1 << M)
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  if constexpr (M == 0) // quad_perm [1, 0, 3, 2]
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xf, 0xf, false));
+  else if constexpr (M == 1) // quad_perm [2, 3, 0, 1]
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xf, 0xf, false));
+  else // ds_swizzle, bit mode: and 0x1f, or 0, xor 4 (the crossbar of the LDS unit; no LDS memory)
+    return __hiloint2double(__builtin_amdgcn_ds_swizzle(hi, 0x101F), __builtin_amdgcn_ds_swizzle(lo, 0x101F));
+}
+
+// slots of a species: gas  rho | vel 1-3 | P | sie | mom 1-3 | E | eint | V;  dust  rho | vel 1-3 | mom 1-3 | V
+template <bool GAS>
+struct Slots {
+  static constexpr int NV = GAS ? 12 : 8, NCODE = GAS ? 8 : 4, CODE0 = GAS ? 0 : ARTEMIS_VAR_DUST_PRIM_DENSITY;
+  static constexpr int slot(int c) { // of variable CODE0 + c
+    constexpr int g[8] = {0, 1, 4, 5, 0, 6, 9, 10}, d[4] = {0, 1, 0, 4};
+    return GAS ? g[c] : d[c];
+  }
+  static constexpr int width(int c) { return (c == 1 || (GAS ? c == 5 : c == 3)) ? 3 : 1; }
+  double q[NV];
+};
+template <int C>
+struct IntC {
+  static constexpr int value = C;
+};
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+  if constexpr (N > 0) {
+    static_for<N - 1>(f);
+    f(IntC<N - 1>{});
+  }
+}
+
+// N = V q of every slot and V of zone (k, j, i), species n
+template <bool CURV, bool GAS>
+__device__ __forceinline__ void level_leaf(const PackView &P, int b, int n, int k, int j, int i, Slots<GAS> &s) {
+  const long c = (static_cast<long>(k) * P.nj + j) * P.ni + i;
+  double hx[3];
+  scale_factors<CURV>(P, b, k, j, i, hx);
+  const double V = make_coords(P, b, k, j, i).volume();
+  if constexpr (GAS) {
+    const GasZone g = load_gas(P, b, n, c);
+    static_for<Slots<GAS>::NCODE>([&](auto cc) {
+      constexpr int code = decltype(cc)::value;
+      gas_components(g, P.gm1, hx, code, [&](int, int d, double v) { s.q[Slots<GAS>::slot(code) + d] = V * v; });
+    });
+  } else {
+    const DustZone g = load_dust(P, b, n, c);
+    static_for<Slots<GAS>::NCODE>([&](auto cc) {
+      constexpr int code = decltype(cc)::value;
+      dust_components(g, hx, Slots<GAS>::CODE0 + code, [&](int, int d, double v) { s.q[Slots<GAS>::slot(code) + d] = V * v; });
+    });
+  }
+  s.q[Slots<GAS>::NV - 1] = V;
+}
+
+template <bool CURV, bool GAS, int S, class OUT>
+__device__ __forceinline__ void level_species(const PackView &P, const FieldSelection &F, int b, int n, int k0, int j0, int i,
+                                              bool store, OUT *o, long ozones) {
+  using SL = Slots<GAS>;
+  const bool ia = P.ie > P.is, ja = P.je > P.js, ka = P.ke > P.ks;
+  const int nbits = (ja ? 1 : 0) + (ka ? 1 : 0), jbit = 0, kbit = ja ? 1 : 0;
+  SL v, sj[S], sk[S];
+  for (int t = 0; t < (1 << (S * nbits)); ++t) { // (wave-uniform: every branch on t below is)
+    int dj = 0, dk = 0;
+#pragma unroll
+    for (int m = 0; m < S; ++m) {
+      if (ja) dj |= ((t >> (m * nbits + jbit)) & 1) << m;
+      if (ka) dk |= ((t >> (m * nbits + kbit)) & 1) << m;
+    }
+    level_leaf<CURV, GAS>(P, b, n, k0 + dk, j0 + dj, i, v);
+    bool carry = true; // the sums of level m are complete: they enter level m + 1
+    static_for<S>([&](auto mm) {
+      constexpr int m = decltype(mm)::value;
+      if (carry) { // the j pair
+        if (!ja) {
+          for (int q = 0; q < SL::NV; ++q) v.q[q] = v.q[q] + 0.0;
+        } else if ((t >> (m * nbits + jbit)) & 1) {
+          for (int q = 0; q < SL::NV; ++q) v.q[q] = sj[m].q[q] + v.q[q];
+        } else {
+          sj[m] = v, carry = false;
         }
       }
-    }
-    for (int m = 0; m < (S.want_dust ? nsd : 0); ++m) {
-      const FluidView &f = P.dust;
-      const int nv = 4 * nsd;
-      double w_d = f.prim[b * nv + m][c];
-      w_d = (w_d > f.dfloor) ? w_d : f.dfloor;
-      const double vel1 = f.prim[b * nv + nsd + 3 * m + 0][c];
-      const double vel2 = f.prim[b * nv + nsd + 3 * m + 1][c];
-      const double vel3 = f.prim[b * nv + nsd + 3 * m + 2][c];
-      for (int e = 0; e < S.nsel; ++e) {
-        const long at = S.comp0[e] * zones;
-        switch (S.code[e]) {
-        case ARTEMIS_VAR_DUST_PRIM_DENSITY:
-        case ARTEMIS_VAR_DUST_CONS_DENSITY: put(o, at + m * zones, w_d); break;
-        case ARTEMIS_VAR_DUST_PRIM_VELOCITY:
-          put(o, at + (3 * m + 0) * zones, vel1), put(o, at + (3 * m + 1) * zones, vel2), put(o, at + (3 * m + 2) * zones, vel3);
-          break;
-        case ARTEMIS_VAR_DUST_CONS_MOMENTUM:
-          put(o, at + (3 * m + 0) * zones, w_d * vel1 * hx[0]);
-          put(o, at + (3 * m + 1) * zones, w_d * vel2 * hx[1]);
-          put(o, at + (3 * m + 2) * zones, w_d * vel3 * hx[2]);
-          break;
-        default: break;
+      if (carry) { // the i pair
+        for (int q = 0; q < SL::NV; ++q) v.q[q] = v.q[q] + (ia ? pair_lane<m>(v.q[q]) : 0.0);
+      }
+      if (carry) { // the k pair
+        if (!ka) {
+          for (int q = 0; q < SL::NV; ++q) v.q[q] = v.q[q] + 0.0;
+        } else if ((t >> (m * nbits + kbit)) & 1) {
+          for (int q = 0; q < SL::NV; ++q) v.q[q] = sk[m].q[q] + v.q[q];
+        } else {
+          sk[m] = v, carry = false;
         }
       }
-    }
+    });
+  }
+  if (!store) return;
+  const double vol = v.q[SL::NV - 1];
+  for (int e = 0; e < F.nsel; ++e) {
+    const long at = F.comp0[e] * ozones;
+    const int code = F.code[e] - SL::CODE0;
+    static_for<SL::NCODE>([&](auto cc) {
+      constexpr int c = decltype(cc)::value, w = SL::width(c);
+      if (code == c)
+        for (int d = 0; d < w; ++d) put(o, at + (w * n + d) * ozones, v.q[SL::slot(c) + d] / vol);
+    });
+  }
+}
+
+template <bool CURV, class OUT, int S>
+__global__ __launch_bounds__(FTX *FTY) void pack_fields_level_kernel(const PackView P, const LevelTiles T, const FieldSelection F,
+                                                                    const LevelBlocks B, int block0, OUT *out) {
+  const bool ia = P.ie > P.is, ja = P.je > P.js, ka = P.ke > P.ks;
+  const long ozones = static_cast<long>(T.nxo) * T.nyo * T.nzo;
+  for (long tile = blockIdx.x; tile < T.ntile; tile += gridDim.x) {
+    const int i = P.is + static_cast<int>(tile % T.gx) * FTX + threadIdx.x; // input zone
+    const int J = static_cast<int>((tile / T.gx) % T.gy) * FTY + threadIdx.y; // output row
+    const long bz = tile / (static_cast<long>(T.gx) * T.gy);
+    const int q = static_cast<int>(bz / T.nzo), K = static_cast<int>(bz % T.nzo);
+    const int b = block0 + B.lb[q];
+    if (J >= T.nyo) continue; // (a whole wave)
+    const int ic = (i < P.ie) ? i : P.ie;
+    const int j0 = P.js + (ja ? J << S : J), k0 = P.ks + (ka ? K << S : K);
+    const int io = ia ? (ic - P.is) >> S : ic - P.is;
+    const bool store = i <= P.ie && (!ia || ((i - P.is) & ((1 << S) - 1)) == 0);
+    OUT *o = out + B.off[q] + (static_cast<long>(K) * T.nyo + J) * T.nxo + io;
+    for (int n = 0; n < (F.want_gas ? P.gas.ns : 0); ++n) level_species<CURV, true, S>(P, F, b, n, k0, j0, ic, store, o, ozones);
+    for (int m = 0; m < (F.want_dust ? P.dust.ns : 0); ++m) level_species<CURV, false, S>(P, F, b, m, k0, j0, ic, store, o, ozones);
+  }
+}
+
+template <bool CURV, class OUT>
+__global__ __launch_bounds__(FTX *FTY) void pack_fields_replicate_kernel(const PackView P, const LevelTiles T, const FieldSelection F,
+                                                                        const LevelBlocks B, int block0, int r, OUT *out) {
+  const int ri = P.ie > P.is ? r : 0, rj = P.je > P.js ? r : 0, rk = P.ke > P.ks ? r : 0;
+  const long ozones = static_cast<long>(T.nxo) * T.nyo * T.nzo;
+  for (long tile = blockIdx.x; tile < T.ntile; tile += gridDim.x) {
+    const int io = static_cast<int>(tile % T.gx) * FTX + threadIdx.x; // output zone
+    const int jo = static_cast<int>((tile / T.gx) % T.gy) * FTY + threadIdx.y;
+    const long bz = tile / (static_cast<long>(T.gx) * T.gy);
+    const int q = static_cast<int>(bz / T.nzo), ko = static_cast<int>(bz % T.nzo);
+    if (io >= T.nxo || jo >= T.nyo) continue;
+    put_zone<CURV>(P, F, block0 + B.lb[q], P.ks + (ko >> rk), P.js + (jo >> rj), P.is + (io >> ri),
+                   out + B.off[q] + (static_cast<long>(ko) * T.nyo + jo) * T.nxo + io, ozones);
   }
 }
 // The inverse (artemis_hip_unpack_fields): the same buffer read, the primitives of the interior zones written.  The
@@ -216,6 +424,50 @@ void launch_unpack_fields(const PackView &P, int block0, int nblocks, const Fiel
     const double *q = static_cast<const double *>(in);
     if (curv) hipLaunchKernelGGL((unpack_fields_kernel<true, double>), g, t, 0, s, P, T, U, block0, q);
     else hipLaunchKernelGGL((unpack_fields_kernel<false, double>), g, t, 0, s, P, T, U, block0, q);
+  }
+}
+
+namespace {
+template <bool CURV, class OUT>
+void launch_level_chunk(const PackView &P, int block0, const FieldSelection &F, const LevelBlocks &B, int shift, OUT *o, hipStream_t s) {
+  const int nx1 = P.ie - P.is + 1, nx2 = P.je - P.js + 1, nx3 = P.ke - P.ks + 1;
+  LevelTiles T;
+  T.nxo = level_extent(nx1, shift), T.nyo = level_extent(nx2, shift), T.nzo = level_extent(nx3, shift);
+  T.gx = ((shift > 0 ? nx1 : T.nxo) + FTX - 1) / FTX, T.gy = (T.nyo + FTY - 1) / FTY;
+  T.ntile = static_cast<long>(T.gx) * T.gy * T.nzo * B.n;
+  if (T.ntile == 0) return;
+  const dim3 t(FTX, FTY), g(static_cast<unsigned>(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG));
+  if (shift == 1) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, B, block0, o);
+  else if (shift == 2) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, B, block0, o);
+  else if (shift == 3) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 3>), g, t, 0, s, P, T, F, B, block0, o);
+  else hipLaunchKernelGGL((pack_fields_replicate_kernel<CURV, OUT>), g, t, 0, s, P, T, F, B, block0, -shift, o);
+}
+} // namespace
+
+// One launch per distinct shift and LEVEL_MAX_BLOCKS blocks of it; off[b]: element offset of block block0 + b in `out`.
+// The caller has checked the shifts (|shift| <= 3, extents divisible).
+void launch_pack_fields_level(const PackView &P, int block0, int nblocks, const FieldSelection &F, bool single, const int *shift,
+                              const long *off, void *out, hipStream_t s) {
+  if (F.ncomp == 0) return;
+  const bool curv = P.coords != ARTEMIS_CARTESIAN;
+  for (int sh = -FIELDS_MAX_SHIFT; sh <= FIELDS_MAX_SHIFT; ++sh) {
+    LevelBlocks B;
+    B.n = 0;
+    for (int b = 0; b <= nblocks; ++b) {
+      if (b < nblocks && shift[b] == sh) B.lb[B.n] = b, B.off[B.n] = off[b], B.n++;
+      if (B.n == LEVEL_MAX_BLOCKS || (b == nblocks && B.n > 0)) {
+        if (single) {
+          float *o = static_cast<float *>(out);
+          if (curv) launch_level_chunk<true>(P, block0, F, B, sh, o, s);
+          else launch_level_chunk<false>(P, block0, F, B, sh, o, s);
+        } else {
+          double *o = static_cast<double *>(out);
+          if (curv) launch_level_chunk<true>(P, block0, F, B, sh, o, s);
+          else launch_level_chunk<false>(P, block0, F, B, sh, o, s);
+        }
+        B.n = 0;
+      }
+    }
   }
 }
 

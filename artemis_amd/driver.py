@@ -258,6 +258,9 @@ def _declare(L):
     L.artemis_sim_gather_fields.restype = l
     L.artemis_sim_gather_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp]
     L.artemis_sim_write_fields.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i]
+    L.artemis_sim_gather_fields_level.restype = l
+    L.artemis_sim_gather_fields_level.argtypes = [vp, i, C.POINTER(C.c_char_p), i, i, vp, C.POINTER(l)]
+    L.artemis_sim_write_fields_level.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i, i]
     L.artemis_sim_scatter_fields.restype = l
     L.artemis_sim_scatter_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp, d]
     L._sim_declared = True
@@ -505,11 +508,32 @@ class Simulation:
         variables = [variables] if isinstance(variables, str) else list(variables)
         return (C.c_char_p * max(len(variables), 1))(*[v.encode() for v in variables]), len(variables)
 
-    def gather(self, variables, single=False):
+    def gather(self, variables, single=False, level=None):
         """The named variables ('gas.prim.density', 'gas.prim.velocity', 'gas.prim.pressure', ...: include/artemis_driver.h
         "field output") of this rank's blocks, interior zones only, as [nblocks_local, ncomp, nz, ny, nx] float64 (float32
-        with single=True).  Formed from the primitives on the device; nothing is materialised and the run is not disturbed."""
+        with single=True).  Formed from the primitives on the device; nothing is materialised and the run is not disturbed.
+        level = an int: every block resampled on the device to the zone size of refinement level `level` (0 the root grid,
+        negative coarser) -- finer blocks by the volume-weighted mean of the reference's restriction, coarser ones by
+        replication -- and returned as a list, in local block order, of [ncomp, nz_b, ny_b, nx_b] views of one buffer.  Each
+        requested component is averaged as formed (a velocity as a velocity): ask for gas.cons.* for the conservative answer."""
         names, n = self._names(variables)
+        if level is not None:
+            self._refresh_dims()
+            off = (C.c_long * (self.nblocks + 1))()
+            nbytes = self.L.artemis_sim_gather_fields_level(self.h, n, names, int(single), int(level), None, off)
+            if nbytes < 0:
+                raise RuntimeError(self.L.artemis_sim_last_error().decode())
+            out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
+            ncomp = self.L.artemis_sim_gather_fields_level(self.h, n, names, int(single), int(level), out.ctypes.data, off)
+            if ncomp < 0:
+                raise RuntimeError(self.L.artemis_sim_last_error().decode())
+            nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
+            blocks = []
+            for b in range(self.nblocks):
+                s = self.block_level(b) - int(level)
+                shape = [m if m == 1 else (m >> s if s >= 0 else m << -s) for m in nx]
+                blocks.append(out[off[b]:off[b + 1]].reshape(ncomp, shape[2], shape[1], shape[0]))
+            return blocks
         nbytes = self.L.artemis_sim_gather_fields(self.h, n, names, int(single), None)
         if nbytes < 0:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
@@ -520,11 +544,16 @@ class Simulation:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
         return out.reshape(self.nblocks, ncomp, self.ke - self.ks + 1, self.je - self.js + 1, self.ie - self.is_ + 1)
 
-    def write_fields(self, path, variables, single=False):
+    def write_fields(self, path, variables, single=False, level=None):
         """One dump of the named variables as a directory at `path` (collective over the ranks of the run; replaces an
-        existing one).  artemis_amd.fields.read_fields reads it."""
+        existing one).  artemis_amd.fields.read_fields reads it.  level = an int: every block resampled to refinement level
+        `level` as in gather (a version-2 dump; FieldDump.uniform() then works on any mesh)."""
         names, n = self._names(variables)
-        if self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single)):
+        if level is None:
+            rc = self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single))
+        else:
+            rc = self.L.artemis_sim_write_fields_level(self.h, os.fspath(path).encode(), n, names, int(single), int(level))
+        if rc:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
 
     def scatter(self, variables, array, time=None):
@@ -581,6 +610,8 @@ class Simulation:
         or the first variable missing for a complete form.  Collective.  Returns the variables taken."""
         from .fields import read_fields
         fd = read_fields(path)
+        if fd.level is not None:
+            raise ValueError("%s was resampled to level %d: not a state" % (path, fd.level))
         have = set(fd.variables)
         names = []
         for fluid, ns, forms in (("gas", self.ns_gas, self._GAS_FORMS), ("dust", self.ns_dust, self._DUST_FORMS)):

@@ -1,23 +1,28 @@
 """Reader of the field dumps the host driver writes (<problem_id>.outN.<counter>.fld, Simulation.write_fields;
 include/artemis_driver.h "field output"): a directory with meta.json -- clock, variables, and one entry per mesh block of
 the global mesh in gid order -- and one raw little-endian part rank<r>.bin per writing rank, [block][component][nz][ny][nx]
-over interior zones.  Needs numpy only and no device."""
+over interior zones.  Version 1: every block has the zones of a mesh block.  Version 2 (write_fields(level=L), a deck's
+`level = L`): every block was resampled to the zone size of refinement level L on the device, so the blocks differ in shape
+-- each entry carries its own nx and the element offset of its first value in its rank's part -- and share one zone size.
+Needs numpy only and no device."""
 import json
 import os
 
 import numpy as np
 
-FORMAT, VERSIONS = "artemis_fld", (1,)
+FORMAT, VERSIONS = "artemis_fld", (1, 2)
 
 
 class FieldDump:
     """time, dt, cycle, coordinates, ndim, gamma, dtype; variables: {name: number of components}; components: {name: their
-    names}; blocks: [{gid, level, bounds, nx}] in gid order."""
+    names}; blocks: [{gid, level, bounds, nx}] in gid order; level: None, or the level a version-2 dump was resampled to."""
 
     def __init__(self, path, meta):
         self.path, self.meta = path, meta
         for k in ("time", "dt", "cycle", "coordinates", "ndim", "gamma"):
             setattr(self, k, meta[k])
+        self.version = meta["version"]
+        self.level = meta["level"] if self.version >= 2 else None
         self.dtype = np.dtype(meta["dtype"])
         self.variables = {v["name"]: v["ncomp"] for v in meta["variables"]}
         self.components = {v["name"]: list(v["components"]) for v in meta["variables"]}
@@ -26,24 +31,30 @@ class FieldDump:
         self.nx = list(meta["nx"])
         self._parts = {}
 
+    def _elements(self, b):
+        return self.ncomp * b["nx"][0] * b["nx"][1] * b["nx"][2]
+
+    def _offset(self, b):
+        """element offset of a block of meta["blocks"] in its rank's part"""
+        return b["offset"] if self.version >= 2 else b["index"] * self._elements(b)
+
     def _part(self, rank):
-        """[blocks of that rank, ncomp, nz, ny, nx] as a read-only memory map"""
+        """the part of that rank as a flat read-only memory map"""
         if rank not in self._parts:
             name = os.path.join(self.path, "rank%d.bin" % rank)
-            nblk = sum(1 for b in self.meta["blocks"] if b["rank"] == rank)
-            shape = (nblk, self.ncomp, self.nx[2], self.nx[1], self.nx[0])
-            want = int(np.prod(shape)) * self.dtype.itemsize
+            mine = [b for b in self.meta["blocks"] if b["rank"] == rank]
+            count = sum(self._elements(b) for b in mine)
+            want = count * self.dtype.itemsize
             if not os.path.isfile(name):
                 raise ValueError("%s: part %s is missing" % (self.path, os.path.basename(name)))
             have = os.path.getsize(name)
-            if have != want:
+            if have != want or any(self._offset(b) + self._elements(b) > count for b in mine):
                 raise ValueError("%s: part %s holds %d bytes, meta.json describes %d (truncated or not of this dump)"
                                  % (self.path, os.path.basename(name), have, want))
-            self._parts[rank] = np.memmap(name, dtype=self.dtype, mode="r", shape=shape) if want else np.empty(shape, self.dtype)
+            self._parts[rank] = np.memmap(name, dtype=self.dtype, mode="r", shape=(count,)) if want else np.empty((0,), self.dtype)
         return self._parts[rank]
 
-    def get(self, name):
-        """[nblocks_global, ncomp of the variable, nz, ny, nx] in gid order"""
+    def _at(self, name):
         if name not in self.variables:
             raise KeyError("%s holds %s, not %s" % (self.path, ", ".join(self.variables), name))
         at = 0
@@ -51,31 +62,56 @@ class FieldDump:
             if v["name"] == name:
                 break
             at += v["ncomp"]
-        n = self.variables[name]
-        out = np.empty((len(self.meta["blocks"]), n, self.nx[2], self.nx[1], self.nx[0]), dtype=self.dtype)
-        for g, b in enumerate(self.meta["blocks"]):
-            out[g] = self._part(b["rank"])[b["index"], at:at + n]
+        return at, self.variables[name]
+
+    def get_blocks(self, name):
+        """The variable block by block, in gid order: a list of [ncomp of the variable, nz_b, ny_b, nx_b] arrays (views of
+        the parts).  Works on every dump."""
+        at, n = self._at(name)
+        out = []
+        for b in self.meta["blocks"]:
+            nx, o = b["nx"], self._offset(b)
+            out.append(self._part(b["rank"])[o:o + self._elements(b)].reshape(self.ncomp, nx[2], nx[1], nx[0])[at:at + n])
+        return out
+
+    def get(self, name):
+        """[nblocks_global, ncomp of the variable, nz, ny, nx] in gid order; ValueError where the blocks differ in shape
+        (a dump at a level of a refined mesh): get_blocks gives them one by one."""
+        at, n = self._at(name)
+        shapes = {tuple(b["nx"]) for b in self.blocks}
+        if len(shapes) > 1:
+            raise ValueError("%s: its blocks differ in shape (%s) and do not form one array: use get_blocks(%r)"
+                             % (self.path, ", ".join(str(list(s)) for s in sorted(shapes)), name))
+        nx = self.blocks[0]["nx"] if self.blocks else self.nx
+        out = np.empty((len(self.meta["blocks"]), n, nx[2], nx[1], nx[0]), dtype=self.dtype)
+        for g, blk in enumerate(self.get_blocks(name)):
+            out[g] = blk
         return out
 
     def uniform(self, name):
-        """One [ncomp, NZ, NY, NX] array of the whole mesh, every block placed by its bounds.  Only where every block is on
-        one refinement level (ValueError otherwise)."""
+        """One [ncomp, NZ, NY, NX] array of the whole mesh, every block placed by its bounds with its own nx.  Every
+        version-2 dump forms one (all its blocks share one zone size); a version-1 dump only where every block is on one
+        refinement level (ValueError otherwise)."""
         levels = {b["level"] for b in self.blocks}
-        if len(levels) != 1:
+        if self.version < 2 and len(levels) != 1:
             raise ValueError("%s: blocks on levels %s do not form one uniform array" % (self.path, sorted(levels)))
-        data = self.get(name)
+        data = self.get_blocks(name)
         lo = [min(b["bounds"][2 * d] for b in self.blocks) for d in range(3)]
         hi = [max(b["bounds"][2 * d + 1] for b in self.blocks) for d in range(3)]
-        w = [self.blocks[0]["bounds"][2 * d + 1] - self.blocks[0]["bounds"][2 * d] for d in range(3)]
-        nblk = [int(round((hi[d] - lo[d]) / w[d])) for d in range(3)]
-        out = np.empty((data.shape[1], nblk[2] * self.nx[2], nblk[1] * self.nx[1], nblk[0] * self.nx[0]), dtype=self.dtype)
-        seen = set()
-        for g, b in enumerate(self.blocks):
-            at = tuple(int(round((b["bounds"][2 * d] - lo[d]) / w[d])) for d in range(3))
-            seen.add(at)
-            o = [at[d] * self.nx[d] for d in range(3)]
-            out[:, o[2]:o[2] + self.nx[2], o[1]:o[1] + self.nx[1], o[0]:o[0] + self.nx[0]] = data[g]
-        if len(seen) != nblk[0] * nblk[1] * nblk[2]:
+        # the zone size, from the first block; every block then starts a whole number of zones from the mesh's corner
+        b0 = self.blocks[0]
+        dz = [(b0["bounds"][2 * d + 1] - b0["bounds"][2 * d]) / b0["nx"][d] for d in range(3)]
+        n = [int(round((hi[d] - lo[d]) / dz[d])) for d in range(3)]
+        out = np.empty((data[0].shape[0], n[2], n[1], n[0]), dtype=self.dtype)
+        filled = 0
+        for b, blk in zip(self.blocks, data):
+            o = [int(round((b["bounds"][2 * d] - lo[d]) / dz[d])) for d in range(3)]
+            m = b["nx"]
+            if any(int(round((b["bounds"][2 * d + 1] - b["bounds"][2 * d]) / dz[d])) != m[d] for d in range(3)):
+                raise ValueError("%s: block %d is not on the zone size of block 0" % (self.path, b["gid"]))
+            out[:, o[2]:o[2] + m[2], o[1]:o[1] + m[1], o[0]:o[0] + m[0]] = blk
+            filled += m[0] * m[1] * m[2]
+        if filled != n[0] * n[1] * n[2]:
             raise ValueError("%s: the blocks do not tile their bounding box" % self.path)
         return out
 

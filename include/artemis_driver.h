@@ -206,7 +206,11 @@ void artemis_sim_checkpoint_seconds(double *out4);
  *                     without `variables`, with a name outside the list or of a fluid the run lacks, or with ghost_zones
  *                     = true is listed as skipped ("no variables", "unknown variable NAME", "ghost_zones is not built") and
  *                     writes nothing.  A shipped `hdf5` block becomes one with the override
- *                     parthenon/outputN/file_type=fld.
+ *                     parthenon/outputN/file_type=fld.  level = L (negative allowed): artemis_sim_write_fields_level, every
+ *                     block on the zone size of refinement level L.  The worst shifts the deck can ever produce -- its
+ *                     finest possible level (numlevel - 1, the deepest static region) and the root grid -- are checked
+ *                     here against the block extents: a block that could need an impossible one is listed as skipped
+ *                     ("level L: a block on level X would need shift s, ...") and never fails in the middle of a run.
  *   anything else     not acted on (never an error); artemis_sim_outputs_describe lists it as skipped.
  * Schedule (parthenon's Outputs, upstream): a block is due after the first cycle that ends with time >= next_time, and
  * next_time then becomes the smallest integer multiple of the block's dt above time; a fresh run writes every block at
@@ -220,7 +224,7 @@ int artemis_sim_enable_outputs(artemis_sim_t *sim, const char *dir);
 int artemis_sim_history_device(artemis_sim_t *sim, double *out);
 /* The output blocks of the deck and their state as one JSON object {"enabled", "dir", "problem_id", "blocks": [{"block",
  * "index", "file_type", "dt", "status", "next_time", "written", "last_cycle", "path"}]}; a `fld` block also has
- * "variables" (the names of its list) and "single_precision".  Returns the length of the text
+ * "variables" (the names of its list), "single_precision" and, if the block has one, "level".  Returns the length of the text
  * (written with its NUL only if capacity exceeds it: call with NULL / 0 for the size), < 0 on error. */
 int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long capacity);
 
@@ -248,6 +252,26 @@ long artemis_sim_gather_fields(artemis_sim_t *sim, int nvar, const char *const *
  * Everything is written into <path>.tmp, which is renamed once every rank has succeeded (an existing dump at `path` is
  * replaced): a directory that is there is complete.  artemis_amd/fields.py reads it.  Returns 0, non-zero on error. */
 int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single);
+/* ---- field output at a level: the same variables with every block resampled, on the device, to the zone size of
+ * refinement level `level` (0 = the root grid; negative = coarser than it) before it leaves the device.  A block on level l
+ * has shift s = l - level: s >= 1 restricts it s times with the volume-weighted mean of the reference's RestrictAverage<GEOM>
+ * (summed volumes: exactly conservative), s <= -1 replicates its zones 2^|s| times (exact copies, no slopes: a dump invents
+ * no gradients), s = 0 leaves it; only directions with more than one zone are halved or doubled (artemis_hip.h,
+ * artemis_hip_pack_fields_level, has the definition).  Each REQUESTED COMPONENT is averaged as formed -- gas.prim.velocity
+ * as a velocity, as the reference's restriction treats primitives in its ghost exchange; gas.cons.* gives the conservative
+ * answer.  So a refined mesh reads as one array, and level = -1 on a one-level mesh is a dump an eighth the size (3-D).
+ * |s| <= 3, and s >= 1 needs every active extent of the block divisible by 2^s: a request that breaks either is an error that
+ * names the block, its level and the rule, before anything is written.  Primitives are read, nothing in the run moves.
+ *
+ * gather_level: the blocks follow each other in host_out in local block order, each as [component][nk'][nj'][ni'];
+ * block_offsets (nblocks_local + 1 longs, or NULL) receives the element offset of every block and the total.  Returns the
+ * number of components; with host_out = NULL only the offsets are filled and the bytes needed are returned.  The staging
+ * buffer (FIELDS_STAGE_MB) takes block ranges by bytes.  < 0 on error.
+ * write_level: artemis_sim_write_fields with "version": 2 in meta.json, which adds "level": L, and whose block entries carry
+ * the "nx" each block was written with and "offset", the element offset of its first value in its rank's part. */
+long artemis_sim_gather_fields_level(artemis_sim_t *sim, int nvar, const char *const *names, int single, int level, void *host_out,
+                                     long *block_offsets);
+int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int level);
 /* scatter: the inverse of gather -- the run takes its state from the caller's arrays, which is this driver's form of
  * "write your own problem generator".  host_in is this rank's blocks in local order, laid out as gather returns them for
  * the same names ([local block][component][nk][nj][ni] over the INTERIOR zones, double or float).  For each fluid the names

@@ -265,6 +265,30 @@ enum artemis_field_var { ARTEMIS_VAR_GAS_PRIM_DENSITY = 0, ARTEMIS_VAR_GAS_PRIM_
 size_t artemis_hip_pack_fields_bytes(const artemis_pack_t *p, int nsel, const int *sel, int single);
 int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                             void *out_dev, void *stream);
+/* The same variables resampled to another refinement level before they leave the device.  shift_host[b - block0] (HOST) is
+ * the shift s = (level of block b) - (level asked for); the blocks follow each other in out_dev in block order, each as
+ * [component][nk'][nj'][ni'] with n' = n >> s (s > 0) or n << -s (s < 0) along the ACTIVE directions -- those with more than
+ * one zone; an inactive direction is never halved or doubled.
+ *   s = 0   the values of artemis_hip_pack_fields.
+ *   s >= 1  the volume-weighted mean of RestrictAverage<GEOM> (utils/refinement/restriction.hpp:42-114), applied s times
+ *           with summed volumes: per zone N = V q (q the component as pack_fields forms it, V = Coords::Volume, on
+ *           Cartesian packs too the per-cell product of the face differences), then N and V each go s times up the
+ *           reference's tree ((c000 + c010) + (c001 + c011)) + ((c100 + c110) + (c101 + c111)), c[ok][oj][oi] the child at
+ *           (2K + ok, 2J + oj, 2I + oi) and the literal 0.0 for the offset-1 children of an inactive direction (added as
+ *           the reference adds it: a -0.0 sum becomes +0.0); the output is N / V, one division, then the narrowing.  s = 1
+ *           is RestrictAverage itself; s > 1 is its exactly conservative form (the volumes summed, not those of the
+ *           intermediate grids recomputed, so no geometry of a level the pack does not hold is needed).
+ *   s <= -1 out(k, j, i) = q(k >> |s|, j >> |s|, i >> |s|) along the active directions: exact copies, no slopes.
+ * Each REQUESTED COMPONENT is averaged as formed -- gas.prim.velocity as a velocity, which is what the reference's
+ * restriction does to primitives in its ghost exchange; ask for gas.cons.* for the conservative answer.
+ * ARTEMIS_HIP_EINVAL, before anything is written and with the block, its shift and the rule in artemis_hip_last_error():
+ * |s| > 3, s >= 1 on an active extent that 2^s does not divide, no variables, and whatever artemis_hip_pack_fields refuses.
+ * Nothing is written to the pack.  Asynchronous on `stream`.  artemis_hip_pack_fields_level_bytes: the bytes these blocks
+ * take in out_dev; 0 for arguments the call would refuse. */
+size_t artemis_hip_pack_fields_level_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                           const int *shift_host);
+int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                  const int *shift_host, void *out_dev, void *stream);
 /* The inverse: in_dev (DEVICE) holds what artemis_hip_pack_fields writes for the same arguments -- [block - block0]
  * [component][k][j][i] over the interior zones, the components in the order of the codes of `sel`, double or (single != 0)
  * float, widened exactly -- and the PRIMITIVES of the interior zones of blocks [block0, block0 + nblocks) are written from
