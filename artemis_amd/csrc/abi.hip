@@ -342,6 +342,61 @@ int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nbloc
   artemis::launch_pack_fields_level(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, shift_host, off.data(), out_dev, S(stream));
   return after_launch("pack_fields_level");
 }
+// the axes of artemis_hip_reduce_fields: "" and the zones a block leaves, or what is wrong with them
+static std::string reduce_axes(const artemis_pack_t *p, int axes, long &zones) {
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  zones = 1;
+  if (axes < 1 || axes > 7) return "reduce fields: axes = " + std::to_string(axes) + ", a non-empty mask of x1 (1), x2 (2), x3 (4) is taken";
+  for (int d = 0; d < 3; ++d) {
+    if (((axes >> d) & 1) && nx[d] < 2) return "reduce fields: x" + std::to_string(d + 1) + " has one zone and is not a direction to reduce";
+    if (!((axes >> d) & 1)) zones *= nx[d];
+  }
+  return "";
+}
+static bool reduce_sizes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int axes, artemis::FieldSelection &F,
+                         long &zones) {
+  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return false;
+  if (*field_selection(p, nsel, sel, F) || nsel == 0) return false;
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0) return false;
+  return reduce_axes(p, axes, zones).empty();
+}
+size_t artemis_hip_reduce_fields_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes) {
+  artemis::FieldSelection F;
+  long zones;
+  if (!reduce_sizes(p, block0, nblocks, nsel, sel, axes, F, zones)) return 0;
+  return static_cast<size_t>(nblocks) * (F.ncomp + 1) * zones * (single ? sizeof(float) : sizeof(double));
+}
+size_t artemis_hip_reduce_fields_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                            int axes) {
+  artemis::FieldSelection F;
+  long zones;
+  if (!reduce_sizes(p, block0, nblocks, nsel, sel, axes, F, zones)) return 0;
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  return static_cast<size_t>(artemis::reduce_fields_work_elements(nx, nblocks, F.ncomp, axes)) * sizeof(double);
+}
+int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                              void *out_dev, void *work_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldSelection F;
+  const char *bad = field_selection(p, nsel, sel, F);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (nsel == 0) return fail(ARTEMIS_HIP_EINVAL, "reduce fields: no variables");
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
+    return fail(ARTEMIS_HIP_EINVAL, "reduce fields: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
+  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "reduce fields: the primitive tables of the fluids asked for are required");
+  long zones;
+  const std::string rule = reduce_axes(p, axes, zones);
+  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
+  if (nblocks == 0) return 0;
+  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "reduce fields: null out_dev");
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  if (!work_dev && artemis::reduce_fields_work_elements(nx, nblocks, F.ncomp, axes) > 0)
+    return fail(ARTEMIS_HIP_EINVAL, "reduce fields: null work_dev");
+  artemis::launch_reduce_fields(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, axes, out_dev, static_cast<double *>(work_dev),
+                                S(stream));
+  return after_launch("reduce_fields");
+}
 int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                               const void *in_dev, void *stream) {
   if (int rc = validate(p)) return rc;

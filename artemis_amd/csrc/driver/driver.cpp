@@ -45,6 +45,11 @@ extern "C" int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int 
 // ... and the kernels that resample them to a refinement level: without them the same tree in a host loop
 extern "C" int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                              const int *shift_host, void *out_dev, void *stream) __attribute__((weak));
+// ... and the kernels that integrate them over chosen directions: without them the same sums in a host loop
+extern "C" int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                                         void *out_dev, void *work_dev, void *stream) __attribute__((weak));
+extern "C" size_t artemis_hip_reduce_fields_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                                       int axes) __attribute__((weak));
 // ... and its inverse, which artemis_sim_scatter_fields sets a state with: without it the same expressions in a host loop
 extern "C" int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                          const void *in_dev, void *stream) __attribute__((weak));
@@ -505,6 +510,10 @@ struct artemis_sim_impl {
                              std::vector<Real> *vol);
   // ... resampled to refinement level `level` (artemis_sim_gather_fields_level); offsets: nb + 1 element offsets or null
   size_t gather_fields_level(const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets);
+  // ... integrated over the directions of `axes` (artemis_sim_gather_fields_reduced); field_work: the device work buffer
+  // of artemis_hip_reduce_fields, allocated by the first reduced gather that needs one
+  DevBuf field_work;
+  size_t gather_fields_reduced(const std::vector<int> &codes, bool single, int axes, void *host_out);
   int finest_level() const { // the finest level this run's mesh can ever hold
     int f = adaptive ? amr_max_level : 0;
     for (const Region &r : regions) f = std::max(f, r.level);
@@ -3753,6 +3762,98 @@ size_t artemis_sim_impl::gather_fields_level(const std::vector<int> &codes, bool
   return total;
 }
 
+// The same gather with every block integrated over the directions of `axes` (bit 0 x1, bit 1 x2, bit 2 x3; artemis_hip.h,
+// artemis_hip_reduce_fields, has the definition): block b is [ncomp + 1][nk'][nj'][ni'] in host_out, the reduced extents 1
+// and the volume W last.  artemis_hip_reduce_fields into the staging buffer, the block ranges cut by bytes of output AND of
+// work, or -- a library without that kernel -- the same sums in a host loop over the downloaded primitives.  Primitives
+// are read and nothing of the run moves.  host_out = NULL: the size only.  Returns the bytes.
+size_t artemis_sim_impl::gather_fields_reduced(const std::vector<int> &codes, bool single, int axes, void *host_out) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  std::vector<int> comp0;
+  int ncomp = 0;
+  for (const int code : codes) {
+    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
+    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
+    comp0.push_back(ncomp), ncomp += n;
+  }
+  if (ncomp == 0) throw std::runtime_error("fields: no variables");
+  const std::string bad = artemis_out::reduce_rule(axes, mbnx);
+  if (!bad.empty()) throw std::runtime_error("reduced fields: " + bad);
+  int o[3];
+  for (int d = 0; d < 3; ++d) o[d] = ((axes >> d) & 1) ? 1 : mbnx[d];
+  const size_t esz = single ? sizeof(float) : sizeof(double);
+  const size_t block_el = static_cast<size_t>(ncomp + 1) * o[0] * o[1] * o[2], block_bytes = block_el * esz;
+  const size_t total = static_cast<size_t>(nb) * block_bytes;
+  if (!host_out || total == 0) return total;
+  if (artemis_hip_reduce_fields && artemis_hip_reduce_fields_work_bytes) {
+    const artemis_pack_t p = make_pack(base);
+    const int nsel = static_cast<int>(codes.size());
+    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
+    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
+    const size_t work1 = artemis_hip_reduce_fields_work_bytes(&p, 0, 1, nsel, codes.data(), single ? 1 : 0, axes); // (linear in the blocks)
+    const size_t per = std::max(std::max(block_bytes, work1), static_cast<size_t>(1));
+    const int chunk = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(nb), cap / per)));
+    for (int b0 = 0; b0 < nb; b0 += chunk) {
+      const int n = std::min(chunk, nb - b0);
+      const size_t need = (static_cast<size_t>(n) * block_bytes + sizeof(double) - 1) / sizeof(double);
+      const size_t wneed = static_cast<size_t>(n) * work1 / sizeof(double);
+      if (field_stage.n < need) field_stage.alloc(need);
+      if (wneed > 0 && field_work.n < wneed) field_work.alloc(wneed);
+      CK(artemis_hip_reduce_fields(&p, b0, n, nsel, codes.data(), single ? 1 : 0, axes, field_stage.p, field_work.p, stream), "reduce fields");
+      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(b0) * block_bytes, field_stage.p,
+                               static_cast<size_t>(n) * block_bytes, stream), "d2h");
+      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffers)
+    }
+    return total;
+  }
+  std::vector<Real> q, vol, cur, nxt;
+  for (int b = 0; b < nb; ++b) {
+    host_block_components(b, codes, comp0, ncomp, q, &vol);
+    int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
+    const size_t zin = vol.size();
+    cur.assign((static_cast<size_t>(ncomp) + 1) * zin, 0.0); // rows 0 .. ncomp - 1: N = V q, row ncomp: W = V
+    for (int c = 0; c < ncomp; ++c)
+      for (size_t z = 0; z < zin; ++z) cur[c * zin + z] = vol[z] * q[c * zin + z];
+    std::copy(vol.begin(), vol.end(), cur.begin() + static_cast<size_t>(ncomp) * zin);
+    for (int d = 0; d < 3; ++d) {
+      if (!((axes >> d) & 1)) continue;
+      // cur is [rows][len][inner]: x1 rows = (ncomp + 1) nz ny, inner = 1; x2 inner = nx'; x3 inner = ny' nx'
+      const size_t len = static_cast<size_t>(n[d]), inner = d == 0 ? 1 : (d == 1 ? n[0] : static_cast<size_t>(n[0]) * n[1]);
+      const size_t rows = cur.size() / (len * inner);
+      nxt.assign(rows * inner, 0.0);
+      for (size_t r = 0; r < rows; ++r)
+        for (size_t x = 0; x < inner; ++x) {
+          const Real *in = cur.data() + r * len * inner + x;
+          Real acc = 0.0;
+          if (d == 0) { // the butterfly in chunks of 64, the chunks in increasing order
+            for (size_t c0 = 0; c0 < len; c0 += 64) {
+              Real w[64], y[64];
+              for (size_t l = 0; l < 64; ++l) w[l] = (c0 + l < len) ? in[c0 + l] : 0.0;
+              for (int m = 0; m < 6; ++m) {
+                for (int l = 0; l < 64; ++l) y[l] = w[l] + w[l ^ (1 << m)];
+                std::copy(y, y + 64, w);
+              }
+              acc = (c0 == 0) ? w[0] : acc + w[0];
+            }
+          } else { // sequential, from the first element
+            acc = in[0];
+            for (size_t t = 1; t < len; ++t) acc = acc + in[t * inner];
+          }
+          nxt[r * inner + x] = acc;
+        }
+      cur.swap(nxt);
+      n[d] = 1;
+    }
+    if (cur.size() != block_el) throw std::runtime_error("reduced fields: size mismatch");
+    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(b) * block_bytes;
+    for (size_t e = 0; e < cur.size(); ++e) {
+      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(cur[e]);
+      else reinterpret_cast<double *>(ob)[e] = cur[e];
+    }
+  }
+  return total;
+}
+
 // The inverse of gather_fields: `host_in` holds one complete form of the state per fluid (fields_form.hpp) for this rank's
 // interior zones, laid out as gather_fields returns it.  The primitives of the current buffer are written from it -- by
 // artemis_hip_unpack_fields out of the staging buffer, one copy per block range, or in a host loop with the same expressions
@@ -4315,6 +4416,9 @@ size_t scatter_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool si
 size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets) {
   return sim->p->gather_fields_level(codes, single, level, host_out, offsets);
 }
+size_t gather_fields_reduced(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, void *host_out) {
+  return sim->p->gather_fields_reduced(codes, single, axes, host_out);
+}
 FieldsLayout fields_layout(artemis_sim_t *sim) {
   const artemis_sim_impl &S = *sim->p;
   static const char *const names[6] = {"cartesian", "cylindrical", "spherical1D", "spherical2D", "spherical3D", "axisymmetric"};
@@ -4641,6 +4745,30 @@ long artemis_sim_gather_fields_level(artemis_sim_t *s, int nvar, const char *con
       ncomp += n;
     }
     const size_t bytes = s->p->gather_fields_level(codes, single != 0, level, host_out, block_offsets);
+    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
+  };
+  GUARD(gather(), return -1)
+  return ret;
+}
+long artemis_sim_gather_fields_reduced(artemis_sim_t *s, int nvar, const char *const *names, int single, int axes, void *host_out) {
+  long ret = -1;
+  if (!s->dead.empty()) {
+    g_sim_err = s->dead;
+    return -1;
+  }
+  auto gather = [&]() {
+    const artemis_out::Clock c = artemis_out::clock_of(s);
+    std::vector<int> codes;
+    int ncomp = 0;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = artemis_out::field_var_code(name);
+      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
+      if (n == 0) throw std::runtime_error("gather_fields_reduced: unknown variable " + name);
+      codes.push_back(code);
+      ncomp += n;
+    }
+    const size_t bytes = s->p->gather_fields_reduced(codes, single != 0, axes, host_out);
     ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
   };
   GUARD(gather(), return -1)

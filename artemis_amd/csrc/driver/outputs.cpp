@@ -46,6 +46,7 @@ struct OutBlock {
   bool single = false, is_fld = false;
   bool has_level = false; // fld: `level = L`, every block resampled to the zone size of refinement level L (may be negative)
   int level = 0;
+  int reduce = 0; // fld: `reduce = x2,x3`, the mask of the directions every block is integrated over (0: none)
   std::string skip;
 };
 
@@ -123,6 +124,12 @@ void parse_fld(artemis_host::ParameterInput &pin, const Clock &c, OutBlock &b) {
       const std::string rule = level_rule(lv - b.level, c.mbnx);
       if (b.skip.empty() && !rule.empty()) b.skip = "level " + std::to_string(b.level) + ": a block on level " + std::to_string(lv) + " " + rule;
     }
+  }
+  if (pin.DoesParameterExist(b.name, "reduce")) {
+    std::string rule = reduce_parse(pin.GetString(b.name, "reduce"), b.reduce);
+    if (rule.empty()) rule = reduce_rule(b.reduce, c.mbnx);
+    if (rule.empty() && b.has_level) rule = "reduce: a block that also sets level is not built";
+    if (b.skip.empty() && !rule.empty()) b.skip = rule;
   }
   if (!b.skip.empty()) b.kind = SKIPPED;
 }
@@ -243,10 +250,16 @@ void write_file(const std::string &name, const void *data, size_t bytes) {
   if (std::fclose(f) != 0 || bad) throw std::runtime_error("writing " + name + " failed");
 }
 
-// level = null: version 1.  Else version 2: "level", and every block entry carries the nx it was written with and the
-// element offset of its first value in its rank's part (the blocks of a rank follow each other in index order).
-std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single, const int *level) {
-  std::string j = std::string("{\"format\": \"artemis_fld\", \"version\": ") + (level ? "2, \"level\": " + std::to_string(*level) : std::string("1")) +
+// reduce != 0: version 3 -- "reduce": the names of the directions summed over; the variables end with "volume" (W); every
+// block entry carries its reduced nx and its element offset.
+// reduce == 0 and level = null: version 1.
+// reduce == 0 and a level: version 2 -- "level", and every block entry carries the nx it was written with and the element
+// offset of its first value in its rank's part (the blocks of a rank follow each other in index order).
+std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single, const int *level, int reduce) {
+  std::string red;
+  for (int d = 0; d < 3; ++d)
+    if ((reduce >> d) & 1) red += std::string(red.empty() ? "" : ", ") + "\"x" + std::to_string(d + 1) + "\"";
+  std::string j = std::string("{\"format\": \"artemis_fld\", \"version\": ") + (reduce ? "3, \"reduce\": [" + red + "]" : level ? "2, \"level\": " + std::to_string(*level) : std::string("1")) +
                   ", \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
                   ", \"cycle\": " + std::to_string(c.ncycle) + ", \"coordinates\": " + json_str(L.coordinates) +
                   ", \"ndim\": " + std::to_string(L.ndim) + ", \"nghost\": 0, \"dtype\": " + (single ? "\"<f4\"" : "\"<f8\"") +
@@ -264,6 +277,7 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
         j += std::string(n || d ? ", " : "") + json_str(name + "_" + std::to_string(n) + (field_var_is_vector(codes[v]) ? "_x" + std::to_string(d + 1) : ""));
     j += "]}";
   }
+  if (reduce) j += ", {\"name\": \"volume\", \"ncomp\": 1, \"components\": [\"volume\"]}";
   j += "],\n \"blocks\": [";
   int ncomp = 0;
   for (const int code : codes) ncomp += field_var_components(code, c.ns_gas, c.ns_dust);
@@ -280,6 +294,18 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
         at += static_cast<long>(ncomp) * level_extent(L.nx[0], s) * level_extent(L.nx[1], s) * level_extent(L.nx[2], s);
       }
     }
+  }
+  if (reduce) {
+    const int o[3] = {(reduce & 1) ? 1 : L.nx[0], (reduce & 2) ? 1 : L.nx[1], (reduce & 4) ? 1 : L.nx[2]};
+    for (size_t g = 0; g < L.blocks.size(); ++g) {
+      const FieldBlock &B = L.blocks[g];
+      j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
+      for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
+      j += "], \"nx\": [" + std::to_string(o[0]) + ", " + std::to_string(o[1]) + ", " + std::to_string(o[2]) + "], \"offset\": " +
+           std::to_string(static_cast<long>(B.index) * (ncomp + 1) * o[0] * o[1] * o[2]) + ", \"rank\": " + std::to_string(B.rank) +
+           ", \"index\": " + std::to_string(B.index) + "}";
+    }
+    return j + "]}\n";
   }
   for (size_t g = 0; g < L.blocks.size(); ++g) {
     const FieldBlock &B = L.blocks[g];
@@ -301,7 +327,8 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
 
 // One field dump (artemis_driver.h: artemis_sim_write_fields).  Every rank takes every vote, whatever happened to it
 // before: the votes are collective.
-void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single, const int *level = nullptr) {
+void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single, const int *level = nullptr,
+                  int reduce = 0) {
   std::string err, dir = path_in, tmp;
   while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
   tmp = dir + ".tmp";
@@ -322,8 +349,11 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   bool failed = vote(sim, !err.empty());
   if (!failed) {
     try {
-      std::vector<char> host(level ? gather_fields_level(sim, codes, single, *level, nullptr, nullptr) : gather_fields(sim, codes, single, nullptr));
-      if (level) gather_fields_level(sim, codes, single, *level, host.data(), nullptr);
+      std::vector<char> host(reduce  ? gather_fields_reduced(sim, codes, single, reduce, nullptr)
+                             : level ? gather_fields_level(sim, codes, single, *level, nullptr, nullptr)
+                                     : gather_fields(sim, codes, single, nullptr));
+      if (reduce) gather_fields_reduced(sim, codes, single, reduce, host.data());
+      else if (level) gather_fields_level(sim, codes, single, *level, host.data(), nullptr);
       else gather_fields(sim, codes, single, host.data());
       write_file(tmp + "/rank" + std::to_string(c.rank) + ".bin", host.data(), host.size());
     } catch (const std::exception &e) {
@@ -334,7 +364,7 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   if (!failed) {
     try {
       if (c.rank == 0) {
-        const std::string meta = meta_json(c, L, codes, single, level);
+        const std::string meta = meta_json(c, L, codes, single, level, reduce);
         write_file(tmp + "/meta.json", meta.data(), meta.size()); // last: a directory with it has all its parts
         remove_field_dir(dir);
         if (std::rename(tmp.c_str(), dir.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + dir + ": " + std::strerror(errno));
@@ -358,7 +388,7 @@ void write_field_dump(artemis_sim_t *sim, State &st, OutBlock &b, bool final) {
   char num[16];
   std::snprintf(num, sizeof num, "%05ld", b.counter);
   b.path = st.dir + "/" + st.problem_id + ".out" + std::to_string(b.index) + "." + (final ? std::string("final") : std::string(num)) + ".fld";
-  write_fields(sim, b.path, b.codes, b.single, b.has_level ? &b.level : nullptr);
+  write_fields(sim, b.path, b.codes, b.single, b.has_level ? &b.level : nullptr, b.reduce);
   if (!final) b.counter++;
 }
 
@@ -486,6 +516,28 @@ int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nva
   }
 }
 
+int artemis_sim_write_fields_reduced(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes) {
+  using namespace artemis_out;
+  try {
+    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
+    const Clock c = clock_of(sim);
+    std::vector<int> codes;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = field_var_code(name);
+      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
+      codes.push_back(code);
+    }
+    const std::string rule = reduce_rule(axes, c.mbnx); // (every rank holds blocks of the same shape: all refuse or none)
+    if (!rule.empty()) throw std::runtime_error("write_fields: " + rule);
+    write_fields(sim, path, codes, single != 0, nullptr, axes);
+    return 0;
+  } catch (const std::exception &e) {
+    artemis_ckpt::set_error(e.what());
+    return 1;
+  }
+}
+
 long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in, double time) {
   using namespace artemis_out;
   try {
@@ -531,6 +583,12 @@ int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long 
         for (size_t v = 0; v < b.variables.size(); ++v) j += (v ? ", " : "") + json_str(b.variables[v]);
         j += std::string("], \"single_precision\": ") + (b.single ? "true" : "false");
         if (b.has_level) j += ", \"level\": " + std::to_string(b.level);
+        if (b.reduce) {
+          j += ", \"reduce\": [";
+          for (int d = 0, n = 0; d < 3; ++d)
+            if ((b.reduce >> d) & 1) j += std::string(n++ ? ", " : "") + "\"x" + std::to_string(d + 1) + "\"";
+          j += "]";
+        }
       }
       j += "}";
     }

@@ -84,6 +84,34 @@ inline std::string level_rule(int shift, const int nx[3]) {
 // [component][nk'][nj'][ni']; offsets (nblocks_local + 1 longs, or null): element offset of every block and the total.
 // host_out = NULL: sizes only.  Throws, before anything is written, for a block whose shift breaks a rule.
 size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets);
+// ---- ... integrated over chosen directions: `axes` is a mask, bit 0 x1, bit 1 x2, bit 2 x3, of ACTIVE directions
+// "" or what is wrong with a list "x2,x3" (axes filled: the mask)
+inline std::string reduce_parse(const std::string &list, int &axes) {
+  axes = 0;
+  for (size_t at = 0; at <= list.size();) {
+    size_t end = list.find(',', at);
+    if (end == std::string::npos) end = list.size();
+    std::string name = list.substr(at, end - at);
+    const size_t a = name.find_first_not_of(" \t"), z = name.find_last_not_of(" \t");
+    name = a == std::string::npos ? "" : name.substr(a, z - a + 1);
+    if (name == "x1") axes |= 1;
+    else if (name == "x2") axes |= 2;
+    else if (name == "x3") axes |= 4;
+    else if (!name.empty()) return "reduce: unknown direction " + name + " (x1, x2, x3)";
+    at = end + 1;
+  }
+  return axes ? "" : "reduce: no direction";
+}
+// "" or the rule a block of nx zones breaks with these axes
+inline std::string reduce_rule(int axes, const int nx[3]) {
+  if (axes < 1 || axes > 7) return "reduce: no direction";
+  for (int d = 0; d < 3; ++d)
+    if (((axes >> d) & 1) && nx[d] < 2) return "reduce: x" + std::to_string(d + 1) + " has one zone and is not a direction to reduce";
+  return "";
+}
+// (driver.cpp) the gather with every block integrated over `axes`: [local block][component, the volume last][nk'][nj'][ni']
+// with the reduced extents 1.  host_out = NULL: the size only.  Throws, before anything is written, where reduce_rule does.
+size_t gather_fields_reduced(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, void *host_out);
 // (driver.cpp) the inverse: host_in in that layout, holding one complete form of the state per fluid (csrc/fields_form.hpp),
 // becomes the interior primitives of the current buffer -- artemis_hip_unpack_fields out of the same staging buffer, or the
 // host loop -- and the state is completed as a problem generator's is; time = NaN keeps the clock, dt is estimated afresh.

@@ -134,6 +134,12 @@ constexpr int FIELDS_MAX_SHIFT = 3;
 inline int level_extent(int n, int shift) { return n == 1 ? 1 : (shift >= 0 ? n >> shift : n << -shift); }
 void launch_pack_fields_level(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, const int *shift,
                               const long *off, void *out, hipStream_t s);
+// kernels_reduce.hip: the same components integrated over the directions of `axes` (bit 0 x1, bit 1 x2, bit 2 x3; active
+// directions only), a block leaving [ncomp + 1][nz'][ny'][nx'] with the volume last (artemis_hip.h has the definition).
+// `work`: reduce_fields_work_elements doubles, what the passes before the last leave behind them.
+long reduce_fields_work_elements(const int nx[3], int nblocks, int ncomp, int axes);
+void launch_reduce_fields(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, int axes, void *out, double *work,
+                          hipStream_t s);
 // ... and its inverse: the form of each fluid that the buffer holds (fields_form.hpp) written to the interior primitives
 void launch_unpack_fields(const PackView &P, int block0, int nblocks, const FieldUnpack &U, bool single, const void *in, hipStream_t s);
 } // namespace artemis

@@ -13,6 +13,7 @@
 // traffic of a float dump anyway.  A thread loads the primitives of one species once and forms every requested component
 // of that species from them; the selection is wave-uniform, so the switch below does not diverge.
 #include "device_math.hpp"
+#include "fields_device.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
 #include "pack_view.hpp"
@@ -28,75 +29,6 @@ struct FieldTiles {
   int gx, gy, nkr;
   long ntile;
 };
-
-template <class OUT>
-__device__ __forceinline__ void put(OUT *out, long at, double v) {
-  out[at] = static_cast<OUT>(v); // (double -> float: round to nearest even, the correctly rounded narrowing)
-}
-
-// One zone of one species as PrimToCons sees it, and the components of a variable formed from it: the expressions every
-// kernel of this file that forms output values shares (f(width, d, v): component d of a variable of `width` components a
-// species).
-struct GasZone {
-  double w_d, vel1, vel2, vel3, w_s, u_u, ke;
-};
-struct DustZone {
-  double w_d, vel1, vel2, vel3;
-};
-__device__ __forceinline__ GasZone load_gas(const PackView &P, int b, int n, long c) {
-  const FluidView &f = P.gas;
-  const int nsg = f.ns, nv = 6 * nsg;
-  GasZone z;
-  z.w_d = f.prim[b * nv + n][c];
-  z.w_d = (z.w_d > f.dfloor) ? z.w_d : f.dfloor;
-  z.vel1 = f.prim[b * nv + nsg + 3 * n + 0][c];
-  z.vel2 = f.prim[b * nv + nsg + 3 * n + 1][c];
-  z.vel3 = f.prim[b * nv + nsg + 3 * n + 2][c];
-  z.w_s = f.prim[b * nv + 5 * nsg + n][c];
-  z.w_s = (z.w_s > f.siefloor) ? z.w_s : f.siefloor;
-  z.u_u = z.w_s * z.w_d;
-  z.ke = 0.5 * z.w_d * (sqr(z.vel1) + sqr(z.vel2) + sqr(z.vel3));
-  return z;
-}
-__device__ __forceinline__ DustZone load_dust(const PackView &P, int b, int m, long c) {
-  const FluidView &f = P.dust;
-  const int nsd = f.ns, nv = 4 * nsd;
-  DustZone z;
-  z.w_d = f.prim[b * nv + m][c];
-  z.w_d = (z.w_d > f.dfloor) ? z.w_d : f.dfloor;
-  z.vel1 = f.prim[b * nv + nsd + 3 * m + 0][c];
-  z.vel2 = f.prim[b * nv + nsd + 3 * m + 1][c];
-  z.vel3 = f.prim[b * nv + nsd + 3 * m + 2][c];
-  return z;
-}
-template <class F>
-__device__ __forceinline__ void gas_components(const GasZone &z, double gm1, const double hx[3], int code, F &&f) {
-  switch (code) {
-  case ARTEMIS_VAR_GAS_PRIM_DENSITY:
-  case ARTEMIS_VAR_GAS_CONS_DENSITY: f(1, 0, z.w_d); break;
-  case ARTEMIS_VAR_GAS_PRIM_VELOCITY: f(3, 0, z.vel1), f(3, 1, z.vel2), f(3, 2, z.vel3); break;
-  case ARTEMIS_VAR_GAS_PRIM_PRESSURE: f(1, 0, amax(0.0, gm1 * z.w_d * z.w_s)); break;
-  case ARTEMIS_VAR_GAS_PRIM_SIE: f(1, 0, z.w_s); break;
-  case ARTEMIS_VAR_GAS_CONS_MOMENTUM:
-    f(3, 0, z.w_d * z.vel1 * hx[0]), f(3, 1, z.w_d * z.vel2 * hx[1]), f(3, 2, z.w_d * z.vel3 * hx[2]);
-    break;
-  case ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY: f(1, 0, z.u_u + z.ke); break;
-  case ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY: f(1, 0, z.u_u); break;
-  default: break;
-  }
-}
-template <class F>
-__device__ __forceinline__ void dust_components(const DustZone &z, const double hx[3], int code, F &&f) {
-  switch (code) {
-  case ARTEMIS_VAR_DUST_PRIM_DENSITY:
-  case ARTEMIS_VAR_DUST_CONS_DENSITY: f(1, 0, z.w_d); break;
-  case ARTEMIS_VAR_DUST_PRIM_VELOCITY: f(3, 0, z.vel1), f(3, 1, z.vel2), f(3, 2, z.vel3); break;
-  case ARTEMIS_VAR_DUST_CONS_MOMENTUM:
-    f(3, 0, z.w_d * z.vel1 * hx[0]), f(3, 1, z.w_d * z.vel2 * hx[1]), f(3, 2, z.w_d * z.vel3 * hx[2]);
-    break;
-  default: break;
-  }
-}
 
 // every requested component of zone (k, j, i) of block b, component c at o[c * zones]
 template <bool CURV, class OUT>
@@ -172,63 +104,6 @@ struct LevelTiles {
   long ntile;
 };
 static_assert(sizeof(PackView) + sizeof(FieldSelection) + sizeof(LevelBlocks) + sizeof(LevelTiles) + 64 <= 4096, "kernel arguments");
-
-template <int M>
-__device__ __forceinline__ double pair_lane(double v) { // v of lane ^ (1 << M)
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  if constexpr (M == 0) // quad_perm [1, 0, 3, 2]
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xf, 0xf, false));
-  else if constexpr (M == 1) // quad_perm [2, 3, 0, 1]
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xf, 0xf, false));
-  else // ds_swizzle, bit mode: and 0x1f, or 0, xor 4 (the crossbar of the LDS unit; no LDS memory)
-    return __hiloint2double(__builtin_amdgcn_ds_swizzle(hi, 0x101F), __builtin_amdgcn_ds_swizzle(lo, 0x101F));
-}
-
-// slots of a species: gas  rho | vel 1-3 | P | sie | mom 1-3 | E | eint | V;  dust  rho | vel 1-3 | mom 1-3 | V
-template <bool GAS>
-struct Slots {
-  static constexpr int NV = GAS ? 12 : 8, NCODE = GAS ? 8 : 4, CODE0 = GAS ? 0 : ARTEMIS_VAR_DUST_PRIM_DENSITY;
-  static constexpr int slot(int c) { // of variable CODE0 + c
-    constexpr int g[8] = {0, 1, 4, 5, 0, 6, 9, 10}, d[4] = {0, 1, 0, 4};
-    return GAS ? g[c] : d[c];
-  }
-  static constexpr int width(int c) { return (c == 1 || (GAS ? c == 5 : c == 3)) ? 3 : 1; }
-  double q[NV];
-};
-template <int C>
-struct IntC {
-  static constexpr int value = C;
-};
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (N > 0) {
-    static_for<N - 1>(f);
-    f(IntC<N - 1>{});
-  }
-}
-
-// N = V q of every slot and V of zone (k, j, i), species n
-template <bool CURV, bool GAS>
-__device__ __forceinline__ void level_leaf(const PackView &P, int b, int n, int k, int j, int i, Slots<GAS> &s) {
-  const long c = (static_cast<long>(k) * P.nj + j) * P.ni + i;
-  double hx[3];
-  scale_factors<CURV>(P, b, k, j, i, hx);
-  const double V = make_coords(P, b, k, j, i).volume();
-  if constexpr (GAS) {
-    const GasZone g = load_gas(P, b, n, c);
-    static_for<Slots<GAS>::NCODE>([&](auto cc) {
-      constexpr int code = decltype(cc)::value;
-      gas_components(g, P.gm1, hx, code, [&](int, int d, double v) { s.q[Slots<GAS>::slot(code) + d] = V * v; });
-    });
-  } else {
-    const DustZone g = load_dust(P, b, n, c);
-    static_for<Slots<GAS>::NCODE>([&](auto cc) {
-      constexpr int code = decltype(cc)::value;
-      dust_components(g, hx, Slots<GAS>::CODE0 + code, [&](int, int d, double v) { s.q[Slots<GAS>::slot(code) + d] = V * v; });
-    });
-  }
-  s.q[Slots<GAS>::NV - 1] = V;
-}
 
 template <bool CURV, bool GAS, int S, class OUT>
 __device__ __forceinline__ void level_species(const PackView &P, const FieldSelection &F, int b, int n, int k0, int j0, int i,

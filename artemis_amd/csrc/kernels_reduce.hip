@@ -1,0 +1,255 @@
+// Reduced field output (artemis_hip_reduce_fields): the requested components integrated over chosen directions of every
+// block of a range.  include/artemis_hip.h has the definition; it fixes the bits, this file only has to produce them.
+//
+// Per interior zone and requested component c the leaf is N_c = V q_c, q_c the double pack_fields_kernel stores (the shared
+// expressions of fields_device.hpp) and V = Coords::Volume, and W = V.  N_c and W are summed one direction at a time, x1
+// first, then x2, then x3, the directions not asked for skipped; a block leaves [ncomp + 1][nz'][ny'][nx'], W last.
+//
+// The FIRST pass reads the primitives and is the hot one -- every later pass reads arrays smaller by a whole extent.  It
+// keeps the read side of pack_fields_kernel: lanes along x1, 64 to a wave, 8-byte loads, the primitives of a species read
+// once per zone, all slots of a species in registers with static indices (Slots<GAS>, as the level kernel carries them).
+//   x1 reduced (reduce_fields_kernel<.., 0>)   a wave owns one row (k, j).  It walks the row in chunks of 64 zones from the
+//       interior's first zone; lanes past the row's end hold the literal 0.0; six exchanges x' = x + x[lane ^ (1 << m)],
+//       m = 0..5 (DPP quad_perm, DPP row_ror:8, ds_swizzle, ds_bpermute: register traffic, no LDS memory), leave the
+//       chunk's sum in every lane; the chunks are added in increasing order.  Rows past the block's end are whole waves,
+//       so every lane takes every exchange.  Lane 0 stores.
+//   x1 kept (.., 1: x2 first; .., 2: x3 only)   a thread owns a column (i and the other kept index) and walks the reduced
+//       direction itself, acc = x[0]; acc = acc + x[1]; ..., the leaf of the next zone loaded before the current is added.
+// The later passes (reduce_axis_kernel) walk x2 or x3 of a double work array the same way, one thread per output element,
+// four loads ahead of the additions.  Only the last pass narrows to float.  The sums of one direction are independent for
+// every index of the directions still to come: a radial profile of a 256 x 128^2 block is 128 x 128 waves on the rows,
+// then 128 chains of 128, then one of 128 -- never one wave walking a block.
+// No LDS, no atomics, no tickets: no sum's order depends on the launch.  64-bit offsets.
+#include "device_math.hpp"
+#include "fields_device.hpp"
+#include "geometry.hpp"
+#include "kernels.hpp"
+#include "pack_view.hpp"
+#include "task_device.hpp"
+
+namespace artemis {
+
+namespace {
+constexpr int RTX = 64, RTY = 4;
+constexpr long REDUCE_MAX_WG = 2048; // 256 CUs x 8 workgroups; the rest of the tiles by grid stride
+
+struct ReduceTiles {
+  int gx, gy, nxo, nyo, nzo; // tiles of 64 along x1 (1 where x1 is reduced), of 4 along the other kept index; output extents
+  long ntile;
+  unsigned gmask, dmask; // the slots of a gas / dust species the selection needs (bit NV - 1: the volume, always)
+};
+
+template <int M>
+__device__ __forceinline__ double xor_lane(double v) { // v of lane ^ (1 << M) of a 64-lane wave
+  if constexpr (M <= 2) {
+    return pair_lane<M>(v);
+  } else {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    if constexpr (M == 3) // row_ror:8 -- lane (l + 8) % 16 of the row of 16, which is l ^ 8
+      return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x128, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0x128, 0xf, 0xf, false));
+    else if constexpr (M == 4) // ds_swizzle, bit mode: and 0x1f, or 0, xor 16
+      return __hiloint2double(__builtin_amdgcn_ds_swizzle(hi, 0x401F), __builtin_amdgcn_ds_swizzle(lo, 0x401F));
+    else { // ds_bpermute: the other half of the wave (byte address of the source lane)
+      const int from = (static_cast<int>(threadIdx.x) ^ 32) << 2;
+      return __hiloint2double(__builtin_amdgcn_ds_bpermute(from, hi), __builtin_amdgcn_ds_bpermute(from, lo));
+    }
+  }
+}
+// the sum of a chunk of 64, in every lane: a + b and b + a are the same bits
+__device__ __forceinline__ double chunk_sum(double v) {
+  static_for<6>([&](auto mm) { v = v + xor_lane<decltype(mm)::value>(v); });
+  return v;
+}
+
+// The first pass for one species: DIR = 0 the x1 row of (k, j) in chunks, DIR = 1 the x2 column of (k, i), DIR = 2 the x3
+// column of (j, i); `a` and `c` are the two fixed indices in (k, j, i) order.
+template <bool CURV, bool GAS, int DIR>
+__device__ __forceinline__ void first_pass(const PackView &P, int b, int n, int a, int c, unsigned mask, Slots<GAS> &acc) {
+  using SL = Slots<GAS>;
+  if constexpr (DIR == 0) {
+    const int nx1 = P.ie - P.is + 1;
+    for (int i0 = 0; i0 < nx1; i0 += RTX) { // (wave-uniform)
+      const int i = P.is + i0 + static_cast<int>(threadIdx.x);
+      SL v;
+      level_leaf<CURV, GAS>(P, b, n, a, c, i <= P.ie ? i : P.ie, v);
+      static_for<SL::NV>([&](auto qq) {
+        constexpr int q = decltype(qq)::value;
+        if ((mask >> q) & 1) {
+          const double s = chunk_sum(i <= P.ie ? v.q[q] : 0.0);
+          acc.q[q] = (i0 == 0) ? s : acc.q[q] + s;
+        }
+      });
+    }
+  } else {
+    const int t0 = (DIR == 1) ? P.js : P.ks, t1 = (DIR == 1) ? P.je : P.ke;
+    auto leaf = [&](int t, SL &v) {
+      if constexpr (DIR == 1) level_leaf<CURV, GAS>(P, b, n, a, t, c, v);
+      else level_leaf<CURV, GAS>(P, b, n, t, a, c, v);
+    };
+    SL cur{}, nxt{}; // (value-initialised: the last iteration copies a `nxt` no leaf has filled)
+    leaf(t0, acc);
+    if (t0 < t1) leaf(t0 + 1, cur);
+    for (int t = t0 + 1; t <= t1; ++t) {
+      if (t < t1) leaf(t + 1, nxt); // (issued ahead of the additions below)
+      static_for<SL::NV>([&](auto qq) {
+        constexpr int q = decltype(qq)::value;
+        if ((mask >> q) & 1) acc.q[q] = acc.q[q] + cur.q[q];
+      });
+      cur = nxt;
+    }
+  }
+}
+
+template <bool GAS, class OUT>
+__device__ __forceinline__ void store_species(const FieldSelection &F, int n, const Slots<GAS> &acc, OUT *o, long ozones) {
+  using SL = Slots<GAS>;
+  for (int e = 0; e < F.nsel; ++e) {
+    const long at = F.comp0[e] * ozones;
+    const int code = F.code[e] - SL::CODE0;
+    static_for<SL::NCODE>([&](auto cc) {
+      constexpr int c = decltype(cc)::value, w = SL::width(c);
+      if (code == c)
+        for (int d = 0; d < w; ++d) put(o, at + (w * n + d) * ozones, acc.q[SL::slot(c) + d]);
+    });
+  }
+  put(o, F.ncomp * ozones, acc.q[SL::NV - 1]); // W: the same bits from every species
+}
+
+template <bool CURV, class OUT, int DIR>
+__global__ __launch_bounds__(RTX *RTY) void reduce_fields_kernel(const PackView P, const ReduceTiles T, const FieldSelection F, int block0,
+                                                                OUT *out) {
+  const long ozones = static_cast<long>(T.nxo) * T.nyo * T.nzo;
+  for (long tile = blockIdx.x; tile < T.ntile; tile += gridDim.x) {
+    const int tx = static_cast<int>(tile % T.gx), ty = static_cast<int>((tile / T.gx) % T.gy);
+    const long rest = tile / (static_cast<long>(T.gx) * T.gy);
+    int lb, a, c;     // block of the range and the two fixed indices, (k, j, i) order
+    long z;           // output zone
+    bool store = true;
+    if constexpr (DIR == 0) { // a wave per row: rest = (block, k), ty tiles j
+      lb = static_cast<int>(rest / T.nzo);
+      const int K = static_cast<int>(rest % T.nzo), J = ty * RTY + static_cast<int>(threadIdx.y);
+      if (J >= T.nyo) continue; // (a whole wave)
+      a = P.ks + K, c = P.js + J, z = static_cast<long>(K) * T.nyo + J;
+      store = threadIdx.x == 0;
+    } else if constexpr (DIR == 1) { // thread (k, i): rest = block, ty tiles k
+      lb = static_cast<int>(rest);
+      const int K = ty * RTY + static_cast<int>(threadIdx.y), I = tx * RTX + static_cast<int>(threadIdx.x);
+      if (K >= T.nzo || I >= T.nxo) continue;
+      a = P.ks + K, c = P.is + I, z = static_cast<long>(K) * T.nxo + I;
+    } else { // thread (j, i): rest = block, ty tiles j
+      lb = static_cast<int>(rest);
+      const int J = ty * RTY + static_cast<int>(threadIdx.y), I = tx * RTX + static_cast<int>(threadIdx.x);
+      if (J >= T.nyo || I >= T.nxo) continue;
+      a = P.js + J, c = P.is + I, z = static_cast<long>(J) * T.nxo + I;
+    }
+    const int b = block0 + lb;
+    OUT *o = out + static_cast<long>(lb) * (F.ncomp + 1) * ozones + z;
+    for (int n = 0; n < (F.want_gas ? P.gas.ns : 0); ++n) {
+      Slots<true> acc{}; // (the slots outside the mask stay 0.0 and are never stored)
+      first_pass<CURV, true, DIR>(P, b, n, a, c, T.gmask, acc);
+      if (store) store_species<true>(F, n, acc, o, ozones);
+    }
+    for (int m = 0; m < (F.want_dust ? P.dust.ns : 0); ++m) {
+      Slots<false> acc{};
+      first_pass<CURV, false, DIR>(P, b, m, a, c, T.dmask, acc);
+      if (store) store_species<false>(F, m, acc, o, ozones);
+    }
+  }
+}
+
+// A later pass: in [rows][len][inner] -> out [rows][inner], out(r, x) = in(r, 0, x) + in(r, 1, x) + ... in increasing order
+template <class OUT>
+__global__ __launch_bounds__(256) void reduce_axis_kernel(const double *in, long rows, int len, long inner, OUT *out) {
+  const long total = rows * inner;
+  for (long e = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x; e < total; e += static_cast<long>(gridDim.x) * blockDim.x) {
+    const double *x = in + (e / inner) * len * inner + e % inner;
+    double acc = x[0];
+    int t = 1;
+    for (; t + 3 < len; t += 4) {
+      const double a0 = x[t * inner], a1 = x[(t + 1) * inner], a2 = x[(t + 2) * inner], a3 = x[(t + 3) * inner];
+      acc = acc + a0, acc = acc + a1, acc = acc + a2, acc = acc + a3;
+    }
+    for (; t < len; ++t) acc = acc + x[t * inner];
+    put(out, e, acc);
+  }
+}
+
+template <class SL>
+unsigned slot_mask(const FieldSelection &F) {
+  unsigned m = 1u << (SL::NV - 1);
+  for (int e = 0; e < F.nsel; ++e) {
+    const int c = F.code[e] - SL::CODE0;
+    if (c < 0 || c >= SL::NCODE) continue;
+    for (int d = 0; d < SL::width(c); ++d) m |= 1u << (SL::slot(c) + d);
+  }
+  return m;
+}
+
+template <bool CURV, class OUT>
+void launch_first(const PackView &P, int block0, int nblocks, const FieldSelection &F, int dir, OUT *o, hipStream_t s) {
+  const int nx1 = P.ie - P.is + 1, nx2 = P.je - P.js + 1, nx3 = P.ke - P.ks + 1;
+  ReduceTiles T;
+  T.nxo = dir == 0 ? 1 : nx1, T.nyo = dir == 1 ? 1 : nx2, T.nzo = dir == 2 ? 1 : nx3;
+  T.gx = dir == 0 ? 1 : (nx1 + RTX - 1) / RTX;
+  T.gy = ((dir == 1 ? nx3 : nx2) + RTY - 1) / RTY;
+  T.ntile = static_cast<long>(T.gx) * T.gy * (dir == 0 ? nx3 : 1) * nblocks;
+  T.gmask = slot_mask<Slots<true>>(F), T.dmask = slot_mask<Slots<false>>(F);
+  const dim3 t(RTX, RTY), g(static_cast<unsigned>(T.ntile < REDUCE_MAX_WG ? T.ntile : REDUCE_MAX_WG));
+  if (dir == 0) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 0>), g, t, 0, s, P, T, F, block0, o);
+  else if (dir == 1) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, block0, o);
+  else hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, block0, o);
+}
+
+template <class OUT>
+void launch_axis(const double *in, long rows, int len, long inner, OUT *o, hipStream_t s) {
+  const long total = rows * inner, wg = (total + 255) / 256;
+  hipLaunchKernelGGL((reduce_axis_kernel<OUT>), dim3(static_cast<unsigned>(wg < REDUCE_MAX_WG ? wg : REDUCE_MAX_WG)), dim3(256), 0, s, in, rows,
+                     len, inner, o);
+}
+} // namespace
+
+// doubles of work the passes before the last leave behind them, for nblocks blocks of nx zones and ncomp components
+long reduce_fields_work_elements(const int nx[3], int nblocks, int ncomp, int axes) {
+  long n[3] = {nx[0], nx[1], nx[2]}, total = 0;
+  int left = ((axes >> 0) & 1) + ((axes >> 1) & 1) + ((axes >> 2) & 1);
+  for (int d = 0; d < 3 && left > 1; ++d)
+    if ((axes >> d) & 1) n[d] = 1, --left, total += static_cast<long>(nblocks) * (ncomp + 1) * n[0] * n[1] * n[2];
+  return total;
+}
+
+// The caller has checked `axes` (1..7, active directions only) and the selection (ncomp > 0).
+void launch_reduce_fields(const PackView &P, int block0, int nblocks, const FieldSelection &F, bool single, int axes, void *out, double *work,
+                          hipStream_t s) {
+  if (nblocks == 0 || F.ncomp == 0) return;
+  const bool curv = P.coords != ARTEMIS_CARTESIAN;
+  long n[3] = {P.ie - P.is + 1, P.je - P.js + 1, P.ke - P.ks + 1};
+  int left = ((axes >> 0) & 1) + ((axes >> 1) & 1) + ((axes >> 2) & 1);
+  const long rows0 = static_cast<long>(nblocks) * (F.ncomp + 1);
+  const double *in = nullptr;
+  for (int d = 0; d < 3; ++d) {
+    if (!((axes >> d) & 1)) continue;
+    const bool last = --left == 0, first = in == nullptr;
+    const int len = static_cast<int>(n[d]);
+    n[d] = 1;
+    double *w = work; // where a pass that is not the last leaves its sums
+    if (first) {
+      if (last && single) {
+        float *o = static_cast<float *>(out);
+        if (curv) launch_first<true>(P, block0, nblocks, F, d, o, s);
+        else launch_first<false>(P, block0, nblocks, F, d, o, s);
+      } else {
+        double *o = last ? static_cast<double *>(out) : w;
+        if (curv) launch_first<true>(P, block0, nblocks, F, d, o, s);
+        else launch_first<false>(P, block0, nblocks, F, d, o, s);
+      }
+    } else {
+      // x2 of [rows0][nz][len][nx]: rows = rows0 nz, inner = nx;  x3 of [rows0][len][ny'][nx]: rows = rows0, inner = ny' nx
+      const long rows = d == 1 ? rows0 * n[2] : rows0, inner = d == 1 ? n[0] : n[1] * n[0];
+      if (last && single) launch_axis(in, rows, len, inner, static_cast<float *>(out), s);
+      else launch_axis(in, rows, len, inner, last ? static_cast<double *>(out) : w, s);
+    }
+    in = w, work = w + rows0 * n[0] * n[1] * n[2];
+  }
+}
+
+} // namespace artemis

@@ -261,6 +261,9 @@ def _declare(L):
     L.artemis_sim_gather_fields_level.restype = l
     L.artemis_sim_gather_fields_level.argtypes = [vp, i, C.POINTER(C.c_char_p), i, i, vp, C.POINTER(l)]
     L.artemis_sim_write_fields_level.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i, i]
+    L.artemis_sim_gather_fields_reduced.restype = l
+    L.artemis_sim_gather_fields_reduced.argtypes = [vp, i, C.POINTER(C.c_char_p), i, i, vp]
+    L.artemis_sim_write_fields_reduced.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i, i]
     L.artemis_sim_scatter_fields.restype = l
     L.artemis_sim_scatter_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp, d]
     L._sim_declared = True
@@ -508,15 +511,50 @@ class Simulation:
         variables = [variables] if isinstance(variables, str) else list(variables)
         return (C.c_char_p * max(len(variables), 1))(*[v.encode() for v in variables]), len(variables)
 
-    def gather(self, variables, single=False, level=None):
+    @staticmethod
+    def _axes(reduce, level):
+        """the mask of a `reduce` argument ("x2", ("x2", "x3"), "x2,x3"): 1 = x1, 2 = x2, 4 = x3"""
+        if level is not None:
+            raise ValueError("reduce together with level is not built: splitting a coarse zone's integral across finer "
+                             "output cells needs a rule")
+        names = reduce.split(",") if isinstance(reduce, str) else list(reduce)
+        axes = 0
+        for name in names:
+            name = name.strip()
+            if name not in ("x1", "x2", "x3"):
+                raise ValueError("reduce takes x1, x2 and/or x3, not %r" % (name,))
+            axes |= 1 << (int(name[1]) - 1)
+        if not axes:
+            raise ValueError("reduce names no direction")
+        return axes
+
+    def gather(self, variables, single=False, level=None, reduce=None):
         """The named variables ('gas.prim.density', 'gas.prim.velocity', 'gas.prim.pressure', ...: include/artemis_driver.h
         "field output") of this rank's blocks, interior zones only, as [nblocks_local, ncomp, nz, ny, nx] float64 (float32
         with single=True).  Formed from the primitives on the device; nothing is materialised and the run is not disturbed.
         level = an int: every block resampled on the device to the zone size of refinement level `level` (0 the root grid,
         negative coarser) -- finer blocks by the volume-weighted mean of the reference's restriction, coarser ones by
         replication -- and returned as a list, in local block order, of [ncomp, nz_b, ny_b, nx_b] views of one buffer.  Each
-        requested component is averaged as formed (a velocity as a velocity): ask for gas.cons.* for the conservative answer."""
+        requested component is averaged as formed (a velocity as a velocity): ask for gas.cons.* for the conservative answer.
+        reduce = ("x2", "x3") (any of x1, x2, x3 that have more than one zone): every block integrated over those directions
+        on the device -- per component the sum of V q, and the sum of the volumes V as one more, last, component -- and
+        returned as [nblocks_local, ncomp + 1, nz', ny', nx'] with the reduced extents 1.  The order of the additions is
+        fixed (include/artemis_hip.h, artemis_hip_reduce_fields), so the bits depend on the block alone; a mean is N / W
+        after the blocks that share an output cell have been added.  reduce with level raises ValueError."""
         names, n = self._names(variables)
+        if reduce is not None:
+            axes = self._axes(reduce, level)
+            nbytes = self.L.artemis_sim_gather_fields_reduced(self.h, n, names, int(single), axes, None)
+            if nbytes < 0:
+                raise RuntimeError(self.L.artemis_sim_last_error().decode())
+            self._refresh_dims()
+            out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
+            ncomp = self.L.artemis_sim_gather_fields_reduced(self.h, n, names, int(single), axes, out.ctypes.data)
+            if ncomp < 0:
+                raise RuntimeError(self.L.artemis_sim_last_error().decode())
+            nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
+            shape = [1 if (axes >> q) & 1 else nx[q] for q in range(3)]
+            return out.reshape(self.nblocks, ncomp + 1, shape[2], shape[1], shape[0])
         if level is not None:
             self._refresh_dims()
             off = (C.c_long * (self.nblocks + 1))()
@@ -544,12 +582,15 @@ class Simulation:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
         return out.reshape(self.nblocks, ncomp, self.ke - self.ks + 1, self.je - self.js + 1, self.ie - self.is_ + 1)
 
-    def write_fields(self, path, variables, single=False, level=None):
+    def write_fields(self, path, variables, single=False, level=None, reduce=None):
         """One dump of the named variables as a directory at `path` (collective over the ranks of the run; replaces an
         existing one).  artemis_amd.fields.read_fields reads it.  level = an int: every block resampled to refinement level
-        `level` as in gather (a version-2 dump; FieldDump.uniform() then works on any mesh)."""
+        `level` as in gather (a version-2 dump; FieldDump.uniform() then works on any mesh).  reduce = ("x2", "x3"): every
+        block integrated over those directions as in gather (a version-3 dump; FieldDump.reduced() assembles it)."""
         names, n = self._names(variables)
-        if level is None:
+        if reduce is not None:
+            rc = self.L.artemis_sim_write_fields_reduced(self.h, os.fspath(path).encode(), n, names, int(single), self._axes(reduce, level))
+        elif level is None:
             rc = self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single))
         else:
             rc = self.L.artemis_sim_write_fields_level(self.h, os.fspath(path).encode(), n, names, int(single), int(level))
@@ -612,6 +653,8 @@ class Simulation:
         fd = read_fields(path)
         if fd.level is not None:
             raise ValueError("%s was resampled to level %d: not a state" % (path, fd.level))
+        if fd.reduce is not None:
+            raise ValueError("%s was reduced along %s: not a state" % (path, ", ".join(fd.reduce)))
         have = set(fd.variables)
         names = []
         for fluid, ns, forms in (("gas", self.ns_gas, self._GAS_FORMS), ("dust", self.ns_dust, self._DUST_FORMS)):

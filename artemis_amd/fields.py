@@ -4,25 +4,30 @@ the global mesh in gid order -- and one raw little-endian part rank<r>.bin per w
 over interior zones.  Version 1: every block has the zones of a mesh block.  Version 2 (write_fields(level=L), a deck's
 `level = L`): every block was resampled to the zone size of refinement level L on the device, so the blocks differ in shape
 -- each entry carries its own nx and the element offset of its first value in its rank's part -- and share one zone size.
-Needs numpy only and no device."""
+Version 3 (write_fields(reduce=("x2", "x3")), a deck's `reduce = x2,x3`): every block was integrated over those directions
+on the device -- per component N = sum of V q, and W = sum of V as the last variable, "volume" -- in an order of additions
+that depends on the block alone (include/artemis_hip.h, artemis_hip_reduce_fields); the reduced extents of every nx are 1.
+FieldDump.reduced() adds the blocks and forms the means.  Needs numpy only and no device."""
 import json
 import os
 
 import numpy as np
 
-FORMAT, VERSIONS = "artemis_fld", (1, 2)
+FORMAT, VERSIONS = "artemis_fld", (1, 2, 3)
 
 
 class FieldDump:
     """time, dt, cycle, coordinates, ndim, gamma, dtype; variables: {name: number of components}; components: {name: their
-    names}; blocks: [{gid, level, bounds, nx}] in gid order; level: None, or the level a version-2 dump was resampled to."""
+    names}; blocks: [{gid, level, bounds, nx}] in gid order; level: None, or the level a version-2 dump was resampled to;
+    reduce: None, or the directions (["x2", "x3"]) a version-3 dump was integrated over."""
 
     def __init__(self, path, meta):
         self.path, self.meta = path, meta
         for k in ("time", "dt", "cycle", "coordinates", "ndim", "gamma"):
             setattr(self, k, meta[k])
         self.version = meta["version"]
-        self.level = meta["level"] if self.version >= 2 else None
+        self.level = meta["level"] if self.version == 2 else None
+        self.reduce = list(meta["reduce"]) if self.version == 3 else None
         self.dtype = np.dtype(meta["dtype"])
         self.variables = {v["name"]: v["ncomp"] for v in meta["variables"]}
         self.components = {v["name"]: list(v["components"]) for v in meta["variables"]}
@@ -114,6 +119,54 @@ class FieldDump:
         if filled != n[0] * n[1] * n[2]:
             raise ValueError("%s: the blocks do not tile their bounding box" % self.path)
         return out
+
+    def reduced(self, name, op=None):
+        """A version-3 dump assembled into one [ncomp, NZ, NY, NX] float64 array of the whole mesh, the reduced extents 1:
+        every block is placed by its bounds in the kept directions, and blocks that meet the same output cell are added as
+        float64 in gid order -- the first one assigned, each later one added -- both the integrals N and the volumes W.
+        op = "integral": N; op = "mean": N / W, one division per cell.  gid order is global, so the bits do not depend on
+        the number of ranks that wrote the dump.  On a mesh with several refinement levels the kept directions have no
+        common zone size: only a dump with every active direction reduced (scalars) is assembled, any other is refused.
+        name = "volume" returns W itself, [1, NZ, NY, NX]; it has no mean, so `op` must be "integral" or left at its default
+        (ValueError for an explicit op="mean")."""
+        if self.reduce is None:
+            raise ValueError("%s is not a reduced dump (version %d)" % (self.path, self.version))
+        if name == "volume" and op == "mean":
+            raise ValueError("reduced: the volume is an integral and has no mean")
+        op = "mean" if op is None else op
+        if op not in ("mean", "integral"):
+            raise ValueError("reduced: op is 'mean' or 'integral', not %r" % (op,))
+        axes = {int(a[1]) - 1 for a in self.reduce}
+        kept = [d for d in range(3) if d not in axes and self.nx[d] > 1]
+        levels = sorted({b["level"] for b in self.blocks})
+        if len(levels) != 1 and kept:
+            raise ValueError("%s: blocks on levels %s kept along %s do not share a zone size: only a dump with every active "
+                             "direction reduced is assembled on a refined mesh"
+                             % (self.path, levels, ", ".join("x%d" % (d + 1) for d in kept)))
+        lo = [min(b["bounds"][2 * d] for b in self.blocks) for d in range(3)]
+        hi = [max(b["bounds"][2 * d + 1] for b in self.blocks) for d in range(3)]
+        b0 = self.blocks[0]
+        dz = [(b0["bounds"][2 * d + 1] - b0["bounds"][2 * d]) / b0["nx"][d] for d in range(3)]
+        n = [int(round((hi[d] - lo[d]) / dz[d])) if d in kept else 1 for d in range(3)]
+        num, den = self.get_blocks(name), self.get_blocks("volume")
+        N = np.zeros((num[0].shape[0], n[2], n[1], n[0]), dtype=np.float64)
+        W = np.zeros((1, n[2], n[1], n[0]), dtype=np.float64)
+        seen = np.zeros((n[2], n[1], n[0]), dtype=bool)
+        for b, bn, bw in zip(self.blocks, num, den):
+            o = [int(round((b["bounds"][2 * d] - lo[d]) / dz[d])) if d in kept else 0 for d in range(3)]
+            m = b["nx"]
+            at = (slice(o[2], o[2] + m[2]), slice(o[1], o[1] + m[1]), slice(o[0], o[0] + m[0]))
+            if seen[at].shape != tuple(m[::-1]):
+                raise ValueError("%s: block %d does not lie inside the mesh" % (self.path, b["gid"]))
+            old = seen[at]
+            N[(slice(None),) + at] = np.where(old, N[(slice(None),) + at] + bn.astype(np.float64), bn.astype(np.float64))
+            W[(slice(None),) + at] = np.where(old, W[(slice(None),) + at] + bw.astype(np.float64), bw.astype(np.float64))
+            seen[at] = True
+        if not seen.all():
+            raise ValueError("%s: the blocks do not cover their bounding box" % self.path)
+        if name == "volume":
+            return W
+        return N / W if op == "mean" else N
 
 
 def read_fields(path):

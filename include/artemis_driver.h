@@ -272,6 +272,23 @@ int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, con
 long artemis_sim_gather_fields_level(artemis_sim_t *sim, int nvar, const char *const *names, int single, int level, void *host_out,
                                      long *block_offsets);
 int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int level);
+/* ---- reduced field output: the same variables INTEGRATED over chosen directions, on the device, before they leave it.
+ * `axes` is a non-empty mask of ACTIVE directions (more than one zone): 1 = x1, 2 = x2, 4 = x3.  Per zone and component the
+ * leaf is N = V q (q as gather forms it, V = Coords::Volume) and W = V; both are summed one direction at a time -- x1 as a
+ * butterfly in chunks of 64 zones whose sums are added in increasing order, then x2, then x3 sequentially in increasing
+ * index -- an order that depends on nothing but the block (artemis_hip.h, artemis_hip_reduce_fields, has the definition).
+ * Blocks are not combined and nothing is divided: a mean is N / W after the blocks that meet an output cell have been added
+ * (artemis_amd/fields.py, FieldDump.reduced).  Primitives are read; cons_valid, the clock, the mesh and the run's bits stay.
+ *
+ * gather_reduced: host_out is [local block][ncomp + 1][nk'][nj'][ni'] with the reduced extents 1 and the volume W as the
+ * last component.  Returns the number of components WITHOUT the volume; with host_out = NULL the bytes needed.  The
+ * staging and work buffers (FIELDS_STAGE_MB) take block ranges by bytes.  < 0 on error (axes = 0, an inactive direction).
+ * write_reduced: artemis_sim_write_fields with "version": 3 in meta.json, which adds "reduce": ["x2", "x3"], lists the
+ * variable "volume" last, and whose block entries carry their reduced "nx" and "offset".  A deck's `reduce = x2,x3` in a
+ * `fld` block writes these; a block whose list names an inactive or unknown direction, or that also sets `level`, is listed
+ * as skipped with the reason ("reduce: ...") by artemis_sim_outputs_describe and writes nothing. */
+long artemis_sim_gather_fields_reduced(artemis_sim_t *sim, int nvar, const char *const *names, int single, int axes, void *host_out);
+int artemis_sim_write_fields_reduced(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes);
 /* scatter: the inverse of gather -- the run takes its state from the caller's arrays, which is this driver's form of
  * "write your own problem generator".  host_in is this rank's blocks in local order, laid out as gather returns them for
  * the same names ([local block][component][nk][nj][ni] over the INTERIOR zones, double or float).  For each fluid the names

@@ -289,6 +289,36 @@ size_t artemis_hip_pack_fields_level_bytes(const artemis_pack_t *p, int block0, 
                                            const int *shift_host);
 int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                   const int *shift_host, void *out_dev, void *stream);
+/* Reduced field output: the same variables INTEGRATED over chosen directions before they leave the device.  `axes` is a
+ * non-empty mask of ACTIVE directions (more than one zone): bit 0 x1, bit 1 x2, bit 2 x3.  The definition fixes the bits,
+ * not the launches -- numpy can emulate it bit for bit (tests/fields_reduce_ref.py):
+ *   leaf     per interior zone and requested component c:  N_c = V * q_c  and  W = V, with q_c the double
+ *            artemis_hip_pack_fields forms and V = Coords::Volume of the zone (on Cartesian packs too the per-cell product
+ *            of the face differences, as artemis_hip_pack_fields_level takes it); product and additions are not fused.
+ *   order    N_c and W are reduced one direction at a time, x1 first, then x2, then x3; directions outside `axes` are
+ *            skipped; each direction operates on the result of the one before.
+ *   x1       a butterfly in chunks of 64: the interior row is cut into chunks of 64 zones from its first zone, a short
+ *            last chunk padded with the literal +0.0; inside a chunk six levels m = 0..5 of x'[l] = x[l] + x[l ^ (1 << m)]
+ *            (a + b and b + a are the same bits, so every position ends with the chunk's sum -- equivalently six times
+ *            x[0::2] + x[1::2]); the chunks are then added in increasing order, acc = chunk[0]; acc = acc + chunk[1]; ...
+ *            The 64 is part of the definition, whatever wave does the work.
+ *   x2, x3   sequential in increasing index, acc = x[0]; acc = acc + x[1]; ...  The chain starts from the first element,
+ *            not from 0.0: a row of -0.0 stays -0.0 (the padded x1 butterfly of a short chunk gives +0.0).
+ * out_dev receives, per block of the range in block order, [ncomp + 1][nz'][ny'][nx'] with the reduced extents 1 and the
+ * LAST component W, as double or -- single != 0 -- narrowed to float at the final store (round to nearest).  The device
+ * divides nothing and combines no blocks: a mean is N / W once every block that meets an output cell has been added
+ * (artemis_amd/fields.py, FieldDump.reduced, adds them as float64 in gid order).  No floating-point atomics, no tickets: no
+ * sum's order depends on the launch shape.  work_dev (DEVICE, artemis_hip_reduce_fields_work_bytes; may be NULL where that
+ * is 0) holds what the passes before the last leave.  Offsets are 64-bit.  Nothing is written to the pack.
+ * ARTEMIS_HIP_EINVAL, before anything is written: axes == 0 or outside 1..7, an inactive direction in axes, no variables,
+ * and whatever artemis_hip_pack_fields refuses.  Asynchronous on `stream`.  The two _bytes calls: the bytes these blocks take
+ * in out_dev / work_dev; 0 for arguments the call would refuse. */
+enum { ARTEMIS_REDUCE_X1 = 1, ARTEMIS_REDUCE_X2 = 2, ARTEMIS_REDUCE_X3 = 4 };
+size_t artemis_hip_reduce_fields_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes);
+size_t artemis_hip_reduce_fields_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                            int axes);
+int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                              void *out_dev, void *work_dev, void *stream);
 /* The inverse: in_dev (DEVICE) holds what artemis_hip_pack_fields writes for the same arguments -- [block - block0]
  * [component][k][j][i] over the interior zones, the components in the order of the codes of `sel`, double or (single != 0)
  * float, widened exactly -- and the PRIMITIVES of the interior zones of blocks [block0, block0 + nblocks) are written from
