@@ -178,6 +178,15 @@ class StageGeneralArgs(C.Structure):
     ]
 
 
+class LaunchCut(C.Structure):  # artemis_launch_cut_t
+    _fields_ = [("launcher", C.c_int), ("chunk", C.c_int), ("nchunk", C.c_int), ("workgroups", C.c_int),
+                ("shell_workgroups", C.c_int), ("redo_workgroups", C.c_int)]
+
+
+# enum artemis_cut_launcher
+CUT_NONE, CUT_STAGE_FUSED, CUT_FLUX_FUSED, CUT_STAGE_FUSED_CURV, CUT_STAGE_CURV, CUT_STAGE_PPM, CUT_VISCOUS_SOURCE, CUT_STAGE2D = range(8)
+
+
 class ArtemisHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"artemis_hip error {code}: {msg}")
@@ -241,6 +250,7 @@ def load():
         "artemis_hip_stage_general": (i, [PPk, C.POINTER(StageGeneralArgs), vp]),
         "artemis_hip_stage_general_variant": (i, [PPk, C.POINTER(StageGeneralArgs)]),
         "artemis_hip_stage_general_dust_variant": (i, [PPk, C.POINTER(StageGeneralArgs)]),
+        "artemis_hip_last_launch_cut": (i, [C.POINTER(LaunchCut)]),
         "artemis_hip_stage_epilogue": (i, [PPk, C.POINTER(StageGeneralArgs), vp]),
         "artemis_hip_stage_epilogue_cons": (i, [PPk, C.POINTER(StageGeneralArgs), vp]),
         "artemis_hip_plm_table_count": (C.c_long, [PPk]),
@@ -334,7 +344,7 @@ EXPORTS_HIP = [
     "artemis_hip_ml_floor_ghosts",
     "artemis_hip_ml_face_fluxes", "artemis_hip_ml_stage_fixup", "artemis_hip_plm_table_count", "artemis_hip_plm_table_fill",
     "artemis_hip_drag_source", "artemis_hip_cooling_source", "artemis_hip_cooling_table_fill",
-    "artemis_hip_stage_general", "artemis_hip_stage_general_variant", "artemis_hip_stage_general_dust_variant", "artemis_hip_stage_epilogue", "artemis_hip_stage_epilogue_cons", "artemis_hip_stage_finish", "artemis_hip_stage_finish_cells", "artemis_hip_amr_block_maxima", "artemis_hip_restrict_average",
+    "artemis_hip_stage_general", "artemis_hip_stage_general_variant", "artemis_hip_stage_general_dust_variant", "artemis_hip_last_launch_cut", "artemis_hip_stage_epilogue", "artemis_hip_stage_epilogue_cons", "artemis_hip_stage_finish", "artemis_hip_stage_finish_cells", "artemis_hip_amr_block_maxima", "artemis_hip_restrict_average",
     "artemis_hip_prolongate_minmod", "artemis_hip_amr_first_derivative", "artemis_hip_amr_magnitude",
     "artemis_hip_zero_diffusion_flux", "artemis_hip_viscous_distance_count", "artemis_hip_viscous_distance_fill",
     "artemis_hip_viscous_flux", "artemis_hip_zero_viscous_flux", "artemis_hip_thermal_flux", "artemis_hip_diffusion_update",
@@ -368,6 +378,13 @@ def redo_totals(reset=False):
     out = (C.c_ulonglong * 2)()
     check(load().artemis_hip_redo_totals(out, 1 if reset else 0))
     return int(out[0]), int(out[1])
+
+
+def last_launch_cut():
+    """artemis_hip_last_launch_cut: how the calling thread's most recent march launch cut its work (a LaunchCut)."""
+    c = LaunchCut()
+    check(load().artemis_hip_last_launch_cut(C.byref(c)))
+    return c
 
 
 import contextlib

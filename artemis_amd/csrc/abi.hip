@@ -150,6 +150,10 @@ int ensure_dt_scratch() {
 }
 } // namespace
 
+namespace artemis {
+thread_local LaunchCut g_last_cut; // (kernels.hpp: each march launcher notes its cut here; artemis_hip_last_launch_cut)
+}
+
 extern "C" {
 
 const char *artemis_hip_last_error(void) { return g_err.c_str(); }
@@ -1152,6 +1156,14 @@ int artemis_hip_stage_general_dust_variant(const artemis_pack_t *p, const artemi
   if (p->dust.nspecies == 0) return -1;
   if (a->defer_finish < 0 || a->defer_finish > 2) return 0;
   return stage_plan_of(p, a).dust_code();
+}
+
+int artemis_hip_last_launch_cut(artemis_launch_cut_t *out) {
+  if (!out) return fail(ARTEMIS_HIP_EINVAL, "last launch cut: null out");
+  const artemis::LaunchCut &c = artemis::g_last_cut;
+  out->launcher = c.launcher, out->chunk = c.chunk, out->nchunk = c.nchunk;
+  out->workgroups = c.workgroups, out->shell_workgroups = c.shell_workgroups, out->redo_workgroups = c.redo_workgroups;
+  return 0;
 }
 
 static int stage_epilogue_common(const artemis_pack_t *p, const artemis_stage_general_args_t *a, void *stream, bool to_cons) {

@@ -3,10 +3,34 @@
 #include <hip/hip_runtime.h>
 
 #include "fields_form.hpp"
+#include "options.hpp"
 #include "pack_view.hpp"
 #include "stage_plan.hpp"
 
 namespace artemis {
+// How the calling thread's most recent march launch cut its work (artemis_hip_last_launch_cut): host-side values each
+// march launcher notes as it launches -- nothing of it reaches a kernel.
+struct LaunchCut {
+  int launcher = 0;                                    // enum artemis_cut_launcher (0: no march launched yet)
+  int chunk = 0, nchunk = 0;                           // planes (rows) per chunk and chunks of the main box
+  int workgroups = 0, shell_workgroups = 0, redo_workgroups = 0;
+};
+extern thread_local LaunchCut g_last_cut; // (abi.hip)
+inline void note_cut(int launcher, int chunk, int nchunk, long workgroups, long shell_workgroups = 0, long redo_workgroups = 0) {
+  g_last_cut.launcher = launcher, g_last_cut.chunk = chunk, g_last_cut.nchunk = nchunk;
+  g_last_cut.workgroups = static_cast<int>(workgroups), g_last_cut.shell_workgroups = static_cast<int>(shell_workgroups);
+  g_last_cut.redo_workgroups = static_cast<int>(redo_workgroups);
+}
+// A tuning knob's value as a chunk length: at least one plane, at most `most` (a knob is a long; a value beyond the int
+// range must not wrap into the chunk arithmetic)
+inline int knob_chunk(long value, int most) { return static_cast<int>(value < 1 ? 1 : (value > most ? most : value)); }
+// Workgroups of a grid-stride launch whose own choice is `own`: GRID_CAP, when set, lowers it (never below one), so that
+// a small pack makes every workgroup take several trips of its stride loop -- same bits (the history sums, whose bits
+// follow the number of partial rows by design, excepted)
+inline long grid_capped(long own) {
+  const long cap = opt(OPT_GRID_CAP);
+  return (cap > 0 && cap < own) ? cap : own;
+}
 void launch_calculate_fluxes(const PackView &P, int fluid, int riemann, int recon, hipStream_t s);
 void launch_apply_update(const PackView &P, double gam0, double gam1, double beta_dt, hipStream_t s);
 void launch_flux_source(const PackView &P, int fluid, double dt, hipStream_t s);

@@ -1003,7 +1003,7 @@ void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g,
   const long tiles = static_cast<long>(k.nti) * k.ntj * P.nb;
   // chunks along x3 (one priming trip each): long ones, but enough workgroups for the chip's 512 slots
   int kch = CKMAX;
-  if (opt(OPT_CURV_KCHUNK) > 0) kch = std::min<int>(CKMAX, static_cast<int>(opt(OPT_CURV_KCHUNK)));
+  if (opt(OPT_CURV_KCHUNK) > 0) kch = knob_chunk(opt(OPT_CURV_KCHUNK), CKMAX); // (1 .. CKMAX: the x3 tables in LDS)
   else if (P.ndim > 2) // full rounds of the 512 slots (two workgroups per CU) x few priming trips: kernels.hpp
     kch = (nz + pick_march_chunks(nz, tiles, 512, CKMAX, 0.5) - 1) / pick_march_chunks(nz, tiles, 512, CKMAX, 0.5);
   k.nchunk = (P.ndim > 2) ? (nz + kch - 1) / kch : 1;
@@ -1016,6 +1016,7 @@ void launch_stage_curv(const PackView &P, const artemis_stage_general_args_t &g,
   k.dsum = dust ? nullptr : g.diffusion_sums;
   // (dust: every species marches the same tiles and chunks in the same launch, the species as the grid's slowest index)
   const unsigned grid = static_cast<unsigned>(tiles * k.nchunk * (dust ? P.dust.ns : 1));
+  note_cut(ARTEMIS_CUT_STAGE_CURV, (P.ndim > 2) ? k.kchunk : 1, k.nchunk, grid);
   const int recon = dust ? pl.recon_dust : pl.recon_gas;
   const bool d3 = P.ndim > 2;
 #define CURV_SYS(SYSV, D3V)                                                          \

@@ -1190,7 +1190,9 @@ void launch_viscous_source(const PackView &P, const artemis_diffusion_t &D, doub
   // chunks along x3: two priming trips each, so long ones -- but enough workgroups for two rounds of the chip's slots
   const long tiles = static_cast<long>(a.nti) * a.ntj * P.nb;
   int kch = 32;
-  if (opt(OPT_VISC_KCHUNK) > 0) kch = static_cast<int>(opt(OPT_VISC_KCHUNK));
+  // tuning knob: one plane up to the whole column (the march clamps every plane index into the block and keeps no
+  // per-plane table; the clamp keeps a huge value out of the int arithmetic below)
+  if (opt(OPT_VISC_KCHUNK) > 0) kch = knob_chunk(opt(OPT_VISC_KCHUNK), nz);
   else { // full rounds of the chip's 512 slots (two workgroups per CU), two priming trips per chunk: kernels.hpp
     const int n = pick_march_chunks(nz, tiles, 512, 64, 1.0);
     kch = (nz + n - 1) / n;
@@ -1198,7 +1200,8 @@ void launch_viscous_source(const PackView &P, const artemis_diffusion_t &D, doub
   a.nchunk = (nz + kch - 1) / kch, a.kchunk = (nz + a.nchunk - 1) / a.nchunk;
   a.nchunk = (nz + a.kchunk - 1) / a.kchunk;
   const dim3 grid(static_cast<unsigned>(tiles * a.nchunk)), block(256);
-#define VS_GO(SYS)                                                                                 \
+  note_cut(ARTEMIS_CUT_VISCOUS_SOURCE, a.kchunk, a.nchunk, grid.x);
+#define VS_GO(SYS)                                                                                \
   case SYS:                                                                                       \
     if (narrow) hipLaunchKernelGGL((viscous_source_kernel<SYS, 16>), grid, block, 0, s, P, a);    \
     else hipLaunchKernelGGL((viscous_source_kernel<SYS, 32>), grid, block, 0, s, P, a);           \
@@ -1230,7 +1233,7 @@ void launch_timestep_all(const PackView &P, const artemis_diffusion_t *D, double
   const Box r = interior(P);
   const long per_block = static_cast<long>(r.iu - r.il + 1) * (r.ju - r.jl + 1) * (r.ku - r.kl + 1);
   const long ntile = (per_block + TX * TY - 1) / (TX * TY) * P.nb;
-  const dim3 g(static_cast<unsigned>(ntile < 2048 ? std::max<long>(ntile, 1) : 2048));
+  const dim3 g(static_cast<unsigned>(grid_capped(ntile < 2048 ? std::max<long>(ntile, 1) : 2048)));
   auto *bits = reinterpret_cast<unsigned long long *>(dt_dev);
   artemis_diffcoeff_t off;
   std::memset(&off, 0, sizeof off);
@@ -1247,7 +1250,7 @@ void launch_diffusion_dt(const PackView &P, const artemis_diffusion_t &D, double
   const Box r = interior(P);
   const dim3 g3 = grid_of(r, P.nb);
   const long ntile = static_cast<long>(g3.x) * g3.y * g3.z;
-  const dim3 g(static_cast<unsigned>(ntile < 1024 ? ntile : 1024)); // (one atomicMin per workgroup on ONE address: 512 / 1024 / 4096 / 16384 workgroups: 77 / 52 / 67 / 194 us)
+  const dim3 g(static_cast<unsigned>(grid_capped(ntile < 1024 ? ntile : 1024))); // (one atomicMin per workgroup on ONE address: 512 / 1024 / 4096 / 16384 workgroups: 77 / 52 / 67 / 194 us)
   auto *bits = reinterpret_cast<unsigned long long *>(dt_dev);
   const bool curv = P.coords != ARTEMIS_CARTESIAN;
   for (const artemis_diffcoeff_t *c : {&D.visc, &D.cond}) {

@@ -289,7 +289,7 @@ void launch_unpack_fields(const PackView &P, int block0, int nblocks, const Fiel
   T.gx = (P.ie - P.is + FTX) / FTX, T.gy = (P.je - P.js + FTY) / FTY, T.nkr = P.ke - P.ks + 1;
   T.ntile = static_cast<long>(T.gx) * T.gy * T.nkr * nblocks;
   if (T.ntile == 0 || U.ncomp == 0) return;
-  const dim3 t(FTX, FTY), g(static_cast<unsigned>(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG));
+  const dim3 t(FTX, FTY), g(static_cast<unsigned>(grid_capped(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG)));
   const bool curv = P.coords != ARTEMIS_CARTESIAN;
   if (single) {
     const float *q = static_cast<const float *>(in);
@@ -311,7 +311,7 @@ void launch_level_chunk(const PackView &P, int block0, const FieldSelection &F, 
   T.gx = ((shift > 0 ? nx1 : T.nxo) + FTX - 1) / FTX, T.gy = (T.nyo + FTY - 1) / FTY;
   T.ntile = static_cast<long>(T.gx) * T.gy * T.nzo * B.n;
   if (T.ntile == 0) return;
-  const dim3 t(FTX, FTY), g(static_cast<unsigned>(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG));
+  const dim3 t(FTX, FTY), g(static_cast<unsigned>(grid_capped(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG)));
   if (shift == 1) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, B, block0, o);
   else if (shift == 2) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, B, block0, o);
   else if (shift == 3) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 3>), g, t, 0, s, P, T, F, B, block0, o);
@@ -351,7 +351,7 @@ void launch_pack_fields(const PackView &P, int block0, int nblocks, const FieldS
   T.gx = (P.ie - P.is + FTX) / FTX, T.gy = (P.je - P.js + FTY) / FTY, T.nkr = P.ke - P.ks + 1;
   T.ntile = static_cast<long>(T.gx) * T.gy * T.nkr * nblocks;
   if (T.ntile == 0 || S.ncomp == 0) return;
-  const dim3 t(FTX, FTY), g(static_cast<unsigned>(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG));
+  const dim3 t(FTX, FTY), g(static_cast<unsigned>(grid_capped(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG)));
   const bool curv = P.coords != ARTEMIS_CARTESIAN;
   if (single) {
     float *o = static_cast<float *>(out);

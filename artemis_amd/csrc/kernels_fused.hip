@@ -1457,7 +1457,9 @@ __global__ __launch_bounds__(256) void stage_redo_kernel(const PackView P, const
 // priming trip.  Among 8..16 planes take the best product of round fill and march efficiency (256^3: 16 planes,
 // 4096 workgroups = 8 full rounds; 192 x 128^2: 8 planes, 3 full rounds instead of 1.5).
 int pick_chunk(int planes, long tiles, long slots, int cmax = 16) {
-  if (opt(OPT_FUSED_KCHUNK) > 0) return static_cast<int>(opt(OPT_FUSED_KCHUNK)); // tuning knob
+  // tuning knob: any length from one plane up is legal (the march keeps no per-plane table, and a chunk of one or two
+  // planes still finds its stencil inside the block's nghost >= 2 planes); longer than the box is one chunk
+  if (opt(OPT_FUSED_KCHUNK) > 0) return knob_chunk(opt(OPT_FUSED_KCHUNK), std::max(1, planes));
   int best = 16;
   double score = -1.0;
   // (<= 16 where the launch has a boundary shell, which is one chunk thick; launches without one take up to 128 planes
@@ -1568,10 +1570,11 @@ RedoBufs redo_bufs_of(const PackView &P, const artemis_stage_args_t &a) {
   B.cap = zones;
   return B;
 }
+constexpr unsigned REDO_WG = 32; // workgroups of the exact pass (what artemis_hip_last_launch_cut reports for it)
 template <int RIEMANN, int RECON>
 void launch_redo_cfg(const PackView &P, const RedoK &r, hipStream_t s) {
   // (an empty pass costs by its grid: 5.5 us at 128 workgroups, every stage; the lists are short when they are not empty)
-  hipLaunchKernelGGL((stage_redo_kernel<RIEMANN, RECON>), dim3(32), dim3(256), 0, s, P, r);
+  hipLaunchKernelGGL((stage_redo_kernel<RIEMANN, RECON>), dim3(REDO_WG), dim3(256), 0, s, P, r);
 }
 // artemis_stage_args_t.outflow_faces_by_block (a HOST array) packed into six bits per block; 0: the pack-wide mask applies
 static int pack_outflow(const PackView &P, const artemis_stage_args_t &a, unsigned long long &blk) {
@@ -1719,6 +1722,8 @@ int launch_stage_fused(const PackView &P, const artemis_stage_args_t &a, int rie
   // with gas/de_switch = 0 the equation serves only zones whose total-energy update left no positive internal energy.
   // A positive switch may defer a large share of the zones to the 32-workgroup redo kernel: the full form.
   const bool lean = redo && !opt(OPT_NO_LEAN_ENERGY) && (P.gas.de_switch == 0.0 || opt(OPT_LEAN_ENERGY));
+  // (every refusal is behind us: the cut of a launch that runs; the main box is the last one, the bulk where there is one)
+  note_cut(ARTEMIS_CUT_STAGE_FUSED, k.kchunk[k.nbox - 1], k.nchunk[k.nbox - 1], k.start[k.nbox], k.nshell, redo ? REDO_WG : 0);
   int rc = 4;
 #define RC(RS)                                                                             \
   case RS:                                                                                 \
@@ -1781,6 +1786,7 @@ int launch_flux_fused(const PackView &P, int riemann, int recon, hipStream_t s) 
   k.tiny_in = nullptr, k.tiny_out = nullptr;
   k.outflow = 0, k.outflow_blk = 0, k.outflow_pb = 0;
   k.xcd_swizzle = opt(OPT_FUSED_NO_SWIZZLE) ? 0 : 1;
+  note_cut(ARTEMIS_CUT_FLUX_FUSED, k.kchunk[0], k.nchunk[0], k.start[1]);
 #define RC(RS)                                                                             \
   case RS:                                                                                 \
     if (recon == ARTEMIS_PCM) launch_flux_cfg<RS, 0>(P, k, s);                             \
@@ -1833,6 +1839,7 @@ void launch_stage_fused_curv(const PackView &P, const artemis_stage_general_args
   k.tiny_in = nullptr, k.tiny_out = nullptr;
   k.outflow = 0, k.outflow_blk = 0, k.outflow_pb = 0;
   k.xcd_swizzle = opt(OPT_FUSED_NO_SWIZZLE) ? 0 : 1;
+  note_cut(ARTEMIS_CUT_STAGE_FUSED_CURV, k.kchunk[0], k.nchunk[0], k.start[1]);
   SrcArg<true> src;
   src.v.grav_on = pl.grav_on ? 1 : 0;
   if (src.v.grav_on) src.v.grav = *g.gravity;

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void history_combine_kernel(const double *scrat
 
 long history_workgroups(const PackView &P) {
   const long ntile = hist_tiles(P).ntile;
-  return ntile < HIST_MAX_WG ? ntile : HIST_MAX_WG;
+  return grid_capped(ntile < HIST_MAX_WG ? ntile : HIST_MAX_WG); // (GRID_CAP: fewer rows of partial sums, other bits)
 }
 
 void launch_history_sums(const PackView &P, double *sums, double *scratch, hipStream_t s) {

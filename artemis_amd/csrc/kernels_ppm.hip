@@ -442,10 +442,14 @@ void launch_stage_ppm(const PackView &P, const artemis_stage_general_args_t &g, 
   k.nti = (nx + FTX - 1) / FTX, k.ntj = (ny + FTY - 1) / FTY;
   const long tiles = static_cast<long>(k.nti) * k.ntj * P.nb;
   // chunks along x3 (one priming trip each): long ones, but enough workgroups for the chip's 512 slots (kernels.hpp)
-  const int nch = pick_march_chunks(nz, tiles, 512, PKMAX, 0.6);
+  int nch = pick_march_chunks(nz, tiles, 512, PKMAX, 0.6);
+  // tuning knob (1 .. PKMAX planes: a chunk of any length finds its stencil, planes k0 - 3 .. k1 + 3, inside the block's
+  // nghost >= 3 planes)
+  if (opt(OPT_PPM_KCHUNK) > 0) nch = (nz + knob_chunk(opt(OPT_PPM_KCHUNK), PKMAX) - 1) / knob_chunk(opt(OPT_PPM_KCHUNK), PKMAX);
   k.kchunk = (nz + nch - 1) / nch;
   k.nchunk = (nz + k.kchunk - 1) / k.kchunk;
   const unsigned grid = static_cast<unsigned>(tiles * k.nchunk);
+  note_cut(ARTEMIS_CUT_STAGE_PPM, k.kchunk, k.nchunk, grid);
   if (riemann == ARTEMIS_HLLC) hipLaunchKernelGGL((stage_ppm_kernel<0>), dim3(grid), dim3(256), 0, s, P, k);
   else if (riemann == ARTEMIS_HLLE) hipLaunchKernelGGL((stage_ppm_kernel<1>), dim3(grid), dim3(256), 0, s, P, k);
   else hipLaunchKernelGGL((stage_ppm_kernel<2>), dim3(grid), dim3(256), 0, s, P, k);

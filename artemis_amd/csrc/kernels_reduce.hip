@@ -194,7 +194,7 @@ void launch_first(const PackView &P, int block0, int nblocks, const FieldSelecti
   T.gy = ((dir == 1 ? nx3 : nx2) + RTY - 1) / RTY;
   T.ntile = static_cast<long>(T.gx) * T.gy * (dir == 0 ? nx3 : 1) * nblocks;
   T.gmask = slot_mask<Slots<true>>(F), T.dmask = slot_mask<Slots<false>>(F);
-  const dim3 t(RTX, RTY), g(static_cast<unsigned>(T.ntile < REDUCE_MAX_WG ? T.ntile : REDUCE_MAX_WG));
+  const dim3 t(RTX, RTY), g(static_cast<unsigned>(grid_capped(T.ntile < REDUCE_MAX_WG ? T.ntile : REDUCE_MAX_WG)));
   if (dir == 0) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 0>), g, t, 0, s, P, T, F, block0, o);
   else if (dir == 1) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, block0, o);
   else hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, block0, o);
@@ -203,7 +203,7 @@ void launch_first(const PackView &P, int block0, int nblocks, const FieldSelecti
 template <class OUT>
 void launch_axis(const double *in, long rows, int len, long inner, OUT *o, hipStream_t s) {
   const long total = rows * inner, wg = (total + 255) / 256;
-  hipLaunchKernelGGL((reduce_axis_kernel<OUT>), dim3(static_cast<unsigned>(wg < REDUCE_MAX_WG ? wg : REDUCE_MAX_WG)), dim3(256), 0, s, in, rows,
+  hipLaunchKernelGGL((reduce_axis_kernel<OUT>), dim3(static_cast<unsigned>(grid_capped(wg < REDUCE_MAX_WG ? wg : REDUCE_MAX_WG))), dim3(256), 0, s, in, rows,
                      len, inner, o);
 }
 } // namespace

@@ -706,9 +706,10 @@ void launch_flags(const PackView &P, const S2Args &a, hipStream_t s) {
   // the exact kernel: its waves stride over the listed rows (normally none).  An empty pass of this register-heavy
   // kernel costs by its grid -- 7.4 us at 256 workgroups, 5 % of a 1024^2 stage --, so the grid is sized by the main
   // launch: one exact workgroup per 32 main ones, between 8 and 256
-  const int rg_env = static_cast<int>(opt(OPT_STAGE2D_RGRID));
-  const unsigned rg = rg_env > 0 ? static_cast<unsigned>(rg_env) : std::min(256u, std::max(8u, grid.x / 32u));
+  const long rg_env = opt(OPT_STAGE2D_RGRID); // (tuning knob: any grid from one workgroup up strides over the list)
+  const unsigned rg = rg_env > 0 ? static_cast<unsigned>(knob_chunk(rg_env, 1 << 16)) : std::min(256u, std::max(8u, grid.x / 32u));
   const dim3 rgrid(rg);
+  note_cut(ARTEMIS_CUT_STAGE2D, a.rows, a.nchunk, grid.x, 0, a.redo_cnt ? rg : 0);
 #define GO(U, D)                                                                                                    \
   do {                                                                                                              \
     hipLaunchKernelGGL((stage2d_kernel<RG, RD, RECON, ND, U, D, false>), grid, block, 0, s, P, a);                  \
@@ -773,7 +774,8 @@ void launch_stage2d(const PackView &P, const artemis_stage_general_args_t &g, co
   // chunks until there were 4096 waves, which made 3078 chunks of 6 rows = four rounds of 8 trips, 1.5 x the time).
   int rows = 32;
   if (opt(OPT_STAGE2D_ROWS) > 0) {
-    rows = static_cast<int>(opt(OPT_STAGE2D_ROWS));
+    // tuning knob: one row (what every wave of the exact pass marches) up to the whole strip
+    rows = knob_chunk(opt(OPT_STAGE2D_ROWS), nx2);
   } else {
     const long slots = 1024;
     long best = -1;

@@ -1091,7 +1091,7 @@ void launch_estimate_dt(const PackView &P, int fluid, double cfl, double *dt_dev
   const dim3 t(TX, TY); // fixed 64 x 4 tiles: grid-stride kernel with a wave reduction
   const dim3 g3((r.iu - r.il + TX) / TX, (r.ju - r.jl + TY) / TY, (r.ku - r.kl + 1) * P.nb);
   const long ntile = static_cast<long>(g3.x) * g3.y * g3.z;
-  const dim3 g(static_cast<unsigned>(ntile < 4096 ? ntile : 4096));
+  const dim3 g(static_cast<unsigned>(grid_capped(ntile < 4096 ? ntile : 4096)));
   const bool curv = P.coords != ARTEMIS_CARTESIAN;
   if (fluid == ARTEMIS_GAS) {
     if (curv) hipLaunchKernelGGL((estimate_dt_kernel<0, true>), g, t, 0, s, P, r, cfl, bits);

@@ -20,7 +20,8 @@ namespace artemis {
   X(NO_GRAPH) X(SYNC_LOOP) X(FORCE_OVERLAP) X(LOOPBACK_COMM) X(WAIT_SPIN_LIMIT) X(TEST_SHELL_TARGET_BUMP)  \
   X(HOST_THREADS) X(SETUP_TIMING) X(AMR_DEBUG)                                                        \
   /* tuning knobs */                                                                                  \
-  X(FUSED_KCHUNK) X(CURV_KCHUNK) X(VISC_KCHUNK) X(STAGE2D_ROWS) X(STAGE2D_RGRID) X(FUSED_NO_SWIZZLE)  \
+  X(FUSED_KCHUNK) X(CURV_KCHUNK) X(VISC_KCHUNK) X(PPM_KCHUNK) X(STAGE2D_ROWS) X(STAGE2D_RGRID) X(FUSED_NO_SWIZZLE)  \
+  X(GRID_CAP) /* the grid-stride launches (field packs, reductions, history, timestep limits) take at most this many workgroups */ \
   /* memory */                                                                                        \
   X(NO_POOL) X(POOL_GB) X(TRIM_POOL) X(POISON) X(DENSE_FLUX)                                          \
   X(FIELDS_STAGE_MB) /* cap of the field gather's device staging buffer in MiB (default 256) */

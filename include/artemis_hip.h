@@ -72,8 +72,17 @@
  *    HOST_THREADS=n  host threads of the problem generator; SETUP_TIMING prints its phases; AMR_DEBUG prints the energy
  *                    integral before and after a remesh hand-over
  *  tuning knobs (measurement)
- *    FUSED_KCHUNK, CURV_KCHUNK, VISC_KCHUNK   planes per x3 chunk of the three march kernels
- *    STAGE2D_ROWS, STAGE2D_RGRID, FUSED_NO_SWIZZLE
+ *    FUSED_KCHUNK, CURV_KCHUNK, VISC_KCHUNK, PPM_KCHUNK   planes per x3 chunk of the march kernels (kernels_fused.hip's three
+ *                    launchers: any length from 1, longer than the box = one chunk; kernels_curv.hip: 1 .. 64; the viscous
+ *                    source: 1 .. the whole column; kernels_ppm.hip: 1 .. 64 -- values outside are clamped, and
+ *                    artemis_hip_last_launch_cut reports the cut a launch really took)
+ *    STAGE2D_ROWS    rows per chunk of the 2-D row march (1 .. the whole strip), STAGE2D_RGRID workgroups of its exact pass
+ *    FUSED_NO_SWIZZLE
+ *    GRID_CAP=n      the grid-stride launches (artemis_hip_pack_fields, _pack_fields_level, _unpack_fields, _reduce_fields,
+ *                    _history_sums, _estimate_dt, _timestep_all, _diffusion_dt) take at most n workgroups, so that a small
+ *                    pack makes every workgroup stride over several tiles (tests).  Same bits, except the history sums,
+ *                    whose bits follow the number of partial rows: artemis_hip_history_scratch_bytes follows the cap too,
+ *                    so ask for the scratch size under the value the launch will see
  *  memory
  *    TRIM_POOL       ... and, set, returns what is left in it to the device after every remesh (30 % less footprint; stalls of
  *                    1 - 2 s when a whole size class of slabs goes back at once)
@@ -773,6 +782,21 @@ int artemis_hip_stage_general_variant(const artemis_pack_t *p, const artemis_sta
  * limits on the march's registers; NO_DRAG_IN_MARCH gives 3).  3 and 5 occur only where
  * artemis_hip_stage_general_variant is 3. */
 int artemis_hip_stage_general_dust_variant(const artemis_pack_t *p, const artemis_stage_general_args_t *a);
+/* How the calling thread's most recent march launch cut its work (host-side bookkeeping of the launchers: no launch, no
+ * device access; all zero before the thread's first march).  launcher: which march it was -- a call of
+ * artemis_hip_stage_general with dust on the tile march launches the gas march and then the dust march, and reports the
+ * latter.  chunk / nchunk: planes (2-D row march: rows) per chunk and chunks per tile column (strip) of the launch's main
+ * box -- artemis_hip_stage_fused: its last box, which is the bulk where the launch has one; the last chunk may be shorter.
+ * workgroups: the march kernel's grid; shell_workgroups: how many of them are the boundary shell of a shell-first launch
+ * (the others take the per-XCD id remap unless FUSED_NO_SWIZZLE); redo_workgroups: the grid of the exact pass that follows
+ * (0: none).  The tuning knobs above are clamped to what a kernel can take, and this reports the clamped cut. */
+enum artemis_cut_launcher { ARTEMIS_CUT_NONE = 0, ARTEMIS_CUT_STAGE_FUSED = 1, ARTEMIS_CUT_FLUX_FUSED = 2,
+                            ARTEMIS_CUT_STAGE_FUSED_CURV = 3, ARTEMIS_CUT_STAGE_CURV = 4, ARTEMIS_CUT_STAGE_PPM = 5,
+                            ARTEMIS_CUT_VISCOUS_SOURCE = 6, ARTEMIS_CUT_STAGE2D = 7 };
+typedef struct {
+  int launcher, chunk, nchunk, workgroups, shell_workgroups, redo_workgroups;
+} artemis_launch_cut_t;
+int artemis_hip_last_launch_cut(artemis_launch_cut_t *out);
 /* The cell-local remainder of a stage in ONE pass over stored fluxes: after Gas/Dust::CalculateFluxes
  * (and the diffusion-flux tasks) have filled flux / pflux / vface (/ diff_flux) for p's primitives,
  * this does ApplyUpdate on cons0 / cons1, FluxSource, DiffusionUpdate, ExternalGravity,
