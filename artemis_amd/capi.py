@@ -232,6 +232,9 @@ def load():
         "artemis_hip_reduce_fields_bytes": (C.c_size_t, [PPk, i, i, i, C.POINTER(i), i, i]),
         "artemis_hip_reduce_fields_work_bytes": (C.c_size_t, [PPk, i, i, i, C.POINTER(i), i, i]),
         "artemis_hip_reduce_fields": (i, [PPk, i, i, i, C.POINTER(i), i, i, vp, vp, vp]),
+        "artemis_hip_reduce_fields_level_bytes": (C.c_size_t, [PPk, i, i, i, C.POINTER(i), i, i, C.POINTER(i)]),
+        "artemis_hip_reduce_fields_level_work_bytes": (C.c_size_t, [PPk, i, i, i, C.POINTER(i), i, i, C.POINTER(i)]),
+        "artemis_hip_reduce_fields_level": (i, [PPk, i, i, i, C.POINTER(i), i, i, C.POINTER(i), vp, vp, vp]),
         "artemis_hip_unpack_fields": (i, [PPk, i, i, i, C.POINTER(i), i, vp, vp]),
         "artemis_hip_apply_bc": (i, [PPk, C.POINTER(i), C.POINTER(BcParams), vp]),
         "artemis_hip_external_gravity": (i, [PPk, C.POINTER(Gravity), d, d, vp]),
@@ -337,6 +340,7 @@ EXPORTS_HIP = [
     "artemis_hip_history_scratch_bytes", "artemis_hip_history_sums", "artemis_hip_pack_fields_bytes", "artemis_hip_pack_fields",
     "artemis_hip_unpack_fields", "artemis_hip_pack_fields_level_bytes", "artemis_hip_pack_fields_level",
     "artemis_hip_reduce_fields_bytes", "artemis_hip_reduce_fields_work_bytes", "artemis_hip_reduce_fields",
+    "artemis_hip_reduce_fields_level_bytes", "artemis_hip_reduce_fields_level_work_bytes", "artemis_hip_reduce_fields_level",
     "artemis_hip_apply_bc", "artemis_hip_stage_fused", "artemis_hip_stage_fused_redo_shell", "artemis_hip_redo_totals", "artemis_hip_metric_count",
     "artemis_hip_metric_fill", "artemis_hip_external_gravity", "artemis_hip_nbody_gravity", "artemis_hip_nbody_force_scratch",
     "artemis_hip_nbody_force_sums", "artemis_hip_timestep_all", "artemis_hip_redo_scratch_bytes", "artemis_hip_rotating_frame_force",

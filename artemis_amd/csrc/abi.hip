@@ -401,6 +401,69 @@ int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, int nblocks, 
                                 S(stream));
   return after_launch("reduce_fields");
 }
+// the shifts of artemis_hip_reduce_fields_level: "" and the element offset of every block (off[nblocks]: the total), or what
+// is wrong with the first block that breaks a rule.  Only the KEPT extents (active, outside axes) change with the shift.
+static std::string reduce_level_offsets(const artemis_pack_t *p, int block0, int nblocks, int ncomp, int axes, const int *shift,
+                                        std::vector<long> &off) {
+  off.assign(static_cast<size_t>(nblocks) + 1, 0);
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  for (int b = 0; b < nblocks; ++b) {
+    const int s = shift[b];
+    if (s > artemis::FIELDS_MAX_SHIFT || s < -artemis::FIELDS_MAX_SHIFT)
+      return "reduce fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", |shift| <= 3 is built";
+    long zones = 1;
+    for (int d = 0; d < 3; ++d) {
+      if (s > 0 && !((axes >> d) & 1) && nx[d] > 1 && nx[d] % (1 << s) != 0)
+        return "reduce fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", and its kept nx" +
+               std::to_string(d + 1) + " = " + std::to_string(nx[d]) + " is not divisible by " + std::to_string(1 << s);
+      zones *= artemis::reduce_level_extent(nx[d], s, axes, d);
+    }
+    off[static_cast<size_t>(b) + 1] = off[static_cast<size_t>(b)] + zones * (ncomp + 1);
+  }
+  return "";
+}
+size_t artemis_hip_reduce_fields_level_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                                             const int *shift_host) {
+  artemis::FieldSelection F;
+  long zones;
+  if (!reduce_sizes(p, block0, nblocks, nsel, sel, axes, F, zones) || (nblocks > 0 && !shift_host)) return 0;
+  std::vector<long> off;
+  if (!reduce_level_offsets(p, block0, nblocks, F.ncomp, axes, shift_host, off).empty()) return 0;
+  return static_cast<size_t>(off.back()) * (single ? sizeof(float) : sizeof(double));
+}
+size_t artemis_hip_reduce_fields_level_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                                  int axes, const int *shift_host) {
+  if (artemis_hip_reduce_fields_level_bytes(p, block0, nblocks, nsel, sel, single, axes, shift_host) == 0) return 0;
+  artemis::FieldSelection F;
+  field_selection(p, nsel, sel, F);
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  return static_cast<size_t>(artemis::reduce_fields_level_work_elements(nx, nblocks, F.ncomp, axes)) * sizeof(double);
+}
+int artemis_hip_reduce_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                                    const int *shift_host, void *out_dev, void *work_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldSelection F;
+  const char *bad = field_selection(p, nsel, sel, F);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (nsel == 0) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: no variables");
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
+    return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
+  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: the primitive tables of the fluids asked for are required");
+  long zones;
+  std::string rule = reduce_axes(p, axes, zones);
+  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
+  if (nblocks == 0) return 0;
+  if (!shift_host) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: null shift_host");
+  std::vector<long> off;
+  rule = reduce_level_offsets(p, block0, nblocks, F.ncomp, axes, shift_host, off);
+  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
+  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: null out_dev");
+  if (!work_dev) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: null work_dev");
+  artemis::launch_reduce_fields_level(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, axes, shift_host, off.data(), out_dev,
+                                      static_cast<double *>(work_dev), S(stream));
+  return after_launch("reduce_fields_level");
+}
 int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                               const void *in_dev, void *stream) {
   if (int rc = validate(p)) return rc;

@@ -50,6 +50,11 @@ extern "C" int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, in
                                          void *out_dev, void *work_dev, void *stream) __attribute__((weak));
 extern "C" size_t artemis_hip_reduce_fields_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                                        int axes) __attribute__((weak));
+// ... and the kernel that brings those integrals to a chosen refinement level: without it the same operations in a host loop
+extern "C" int artemis_hip_reduce_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                                               const int *shift_host, void *out_dev, void *work_dev, void *stream) __attribute__((weak));
+extern "C" size_t artemis_hip_reduce_fields_level_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel,
+                                                             int single, int axes, const int *shift_host) __attribute__((weak));
 // ... and its inverse, which artemis_sim_scatter_fields sets a state with: without it the same expressions in a host loop
 extern "C" int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                          const void *in_dev, void *stream) __attribute__((weak));
@@ -514,6 +519,10 @@ struct artemis_sim_impl {
   // of artemis_hip_reduce_fields, allocated by the first reduced gather that needs one
   DevBuf field_work;
   size_t gather_fields_reduced(const std::vector<int> &codes, bool single, int axes, void *host_out);
+  // ... and brought to refinement level `level` along the kept directions (artemis_sim_gather_fields_reduced_level)
+  size_t gather_fields_reduced_level(const std::vector<int> &codes, bool single, int axes, int level, void *host_out, long *offsets);
+  // the host loop of both: block b reduced at its own resolution into cur, [ncomp + 1][n3'][n2'][n1'] doubles, W last
+  void host_reduce_block(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, int axes, std::vector<Real> &cur);
   int finest_level() const { // the finest level this run's mesh can ever hold
     int f = adaptive ? amr_max_level : 0;
     for (const Region &r : regions) f = std::max(f, r.level);
@@ -3762,6 +3771,47 @@ size_t artemis_sim_impl::gather_fields_level(const std::vector<int> &codes, bool
   return total;
 }
 
+void artemis_sim_impl::host_reduce_block(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, int axes,
+                                         std::vector<Real> &cur) {
+  std::vector<Real> q, vol, nxt;
+  host_block_components(b, codes, comp0, ncomp, q, &vol);
+  int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
+  const size_t zin = vol.size();
+  cur.assign((static_cast<size_t>(ncomp) + 1) * zin, 0.0); // rows 0 .. ncomp - 1: N = V q, row ncomp: W = V
+  for (int c = 0; c < ncomp; ++c)
+    for (size_t z = 0; z < zin; ++z) cur[c * zin + z] = vol[z] * q[c * zin + z];
+  std::copy(vol.begin(), vol.end(), cur.begin() + static_cast<size_t>(ncomp) * zin);
+  for (int d = 0; d < 3; ++d) {
+    if (!((axes >> d) & 1)) continue;
+    // cur is [rows][len][inner]: x1 rows = (ncomp + 1) nz ny, inner = 1; x2 inner = nx'; x3 inner = ny' nx'
+    const size_t len = static_cast<size_t>(n[d]), inner = d == 0 ? 1 : (d == 1 ? n[0] : static_cast<size_t>(n[0]) * n[1]);
+    const size_t rows = cur.size() / (len * inner);
+    nxt.assign(rows * inner, 0.0);
+    for (size_t r = 0; r < rows; ++r)
+      for (size_t x = 0; x < inner; ++x) {
+        const Real *in = cur.data() + r * len * inner + x;
+        Real acc = 0.0;
+        if (d == 0) { // the butterfly in chunks of 64, the chunks in increasing order
+          for (size_t c0 = 0; c0 < len; c0 += 64) {
+            Real w[64], y[64];
+            for (size_t l = 0; l < 64; ++l) w[l] = (c0 + l < len) ? in[c0 + l] : 0.0;
+            for (int m = 0; m < 6; ++m) {
+              for (int l = 0; l < 64; ++l) y[l] = w[l] + w[l ^ (1 << m)];
+              std::copy(y, y + 64, w);
+            }
+            acc = (c0 == 0) ? w[0] : acc + w[0];
+          }
+        } else { // sequential, from the first element
+          acc = in[0];
+          for (size_t t = 1; t < len; ++t) acc = acc + in[t * inner];
+        }
+        nxt[r * inner + x] = acc;
+      }
+    cur.swap(nxt);
+    n[d] = 1;
+  }
+}
+
 // The same gather with every block integrated over the directions of `axes` (bit 0 x1, bit 1 x2, bit 2 x3; artemis_hip.h,
 // artemis_hip_reduce_fields, has the definition): block b is [ncomp + 1][nk'][nj'][ni'] in host_out, the reduced extents 1
 // and the volume W last.  artemis_hip_reduce_fields into the staging buffer, the block ranges cut by bytes of output AND of
@@ -3806,46 +3856,117 @@ size_t artemis_sim_impl::gather_fields_reduced(const std::vector<int> &codes, bo
     }
     return total;
   }
-  std::vector<Real> q, vol, cur, nxt;
+  std::vector<Real> cur;
   for (int b = 0; b < nb; ++b) {
-    host_block_components(b, codes, comp0, ncomp, q, &vol);
-    int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
-    const size_t zin = vol.size();
-    cur.assign((static_cast<size_t>(ncomp) + 1) * zin, 0.0); // rows 0 .. ncomp - 1: N = V q, row ncomp: W = V
-    for (int c = 0; c < ncomp; ++c)
-      for (size_t z = 0; z < zin; ++z) cur[c * zin + z] = vol[z] * q[c * zin + z];
-    std::copy(vol.begin(), vol.end(), cur.begin() + static_cast<size_t>(ncomp) * zin);
-    for (int d = 0; d < 3; ++d) {
-      if (!((axes >> d) & 1)) continue;
-      // cur is [rows][len][inner]: x1 rows = (ncomp + 1) nz ny, inner = 1; x2 inner = nx'; x3 inner = ny' nx'
-      const size_t len = static_cast<size_t>(n[d]), inner = d == 0 ? 1 : (d == 1 ? n[0] : static_cast<size_t>(n[0]) * n[1]);
-      const size_t rows = cur.size() / (len * inner);
-      nxt.assign(rows * inner, 0.0);
-      for (size_t r = 0; r < rows; ++r)
-        for (size_t x = 0; x < inner; ++x) {
-          const Real *in = cur.data() + r * len * inner + x;
-          Real acc = 0.0;
-          if (d == 0) { // the butterfly in chunks of 64, the chunks in increasing order
-            for (size_t c0 = 0; c0 < len; c0 += 64) {
-              Real w[64], y[64];
-              for (size_t l = 0; l < 64; ++l) w[l] = (c0 + l < len) ? in[c0 + l] : 0.0;
-              for (int m = 0; m < 6; ++m) {
-                for (int l = 0; l < 64; ++l) y[l] = w[l] + w[l ^ (1 << m)];
-                std::copy(y, y + 64, w);
-              }
-              acc = (c0 == 0) ? w[0] : acc + w[0];
-            }
-          } else { // sequential, from the first element
-            acc = in[0];
-            for (size_t t = 1; t < len; ++t) acc = acc + in[t * inner];
-          }
-          nxt[r * inner + x] = acc;
-        }
-      cur.swap(nxt);
-      n[d] = 1;
-    }
+    host_reduce_block(b, codes, comp0, ncomp, axes, cur);
     if (cur.size() != block_el) throw std::runtime_error("reduced fields: size mismatch");
     char *ob = static_cast<char *>(host_out) + static_cast<size_t>(b) * block_bytes;
+    for (size_t e = 0; e < cur.size(); ++e) {
+      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(cur[e]);
+      else reinterpret_cast<double *>(ob)[e] = cur[e];
+    }
+  }
+  return total;
+}
+
+// The reduced gather on a chosen level (artemis_hip.h, artemis_hip_reduce_fields_level, has the definition): block b is
+// reduced at its own resolution, then brought to shift s = its level - level along the kept directions -- s >= 1 the pair
+// tree x[0::2] + x[1::2] per kept direction, s <= -1 an even share 2^(-|s| m) replicated -- and follows block b - 1 in host_out
+// as [ncomp + 1][nk'][nj'][ni'], W last.  Every shift is checked before anything is written.  The block ranges are cut by
+// bytes of output AND of work; a library without the kernel runs the same operations in the same order in a host loop.
+// offsets (nb + 1 longs, or null): the element offset of every block and the total.  host_out = NULL: sizes only.
+size_t artemis_sim_impl::gather_fields_reduced_level(const std::vector<int> &codes, bool single, int axes, int level, void *host_out,
+                                                     long *offsets) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  std::vector<int> comp0;
+  int ncomp = 0;
+  for (const int code : codes) {
+    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
+    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
+    comp0.push_back(ncomp), ncomp += n;
+  }
+  if (ncomp == 0) throw std::runtime_error("fields: no variables");
+  const std::string bad_axes = artemis_out::reduce_rule(axes, mbnx);
+  if (!bad_axes.empty()) throw std::runtime_error("reduced fields: " + bad_axes);
+  const size_t esz = single ? sizeof(float) : sizeof(double);
+  std::vector<int> shift(static_cast<size_t>(nb));
+  std::vector<long> off(static_cast<size_t>(nb) + 1, 0);
+  for (int b = 0; b < nb; ++b) {
+    const int s = blocks[b].level - level;
+    const std::string bad = artemis_out::reduce_level_rule(s, axes, mbnx);
+    if (!bad.empty())
+      throw std::runtime_error("reduced fields at level " + std::to_string(level) + ": local block " + std::to_string(b) + " (gid " +
+                               std::to_string(blocks[b].gid) + ") on level " + std::to_string(blocks[b].level) + " " + bad);
+    shift[b] = s;
+    long zones = 1;
+    for (int d = 0; d < 3; ++d) zones *= artemis_out::reduce_level_extent(mbnx[d], s, axes, d);
+    off[b + 1] = off[b] + zones * (ncomp + 1);
+  }
+  if (offsets) std::copy(off.begin(), off.end(), offsets);
+  const size_t total = static_cast<size_t>(off[nb]) * esz;
+  if (!host_out || total == 0) return total;
+  bool kept[3];
+  int m = 0, own[3]; // own: the extents the reduction at the block's own resolution leaves
+  for (int d = 0; d < 3; ++d) kept[d] = !((axes >> d) & 1) && mbnx[d] > 1, m += kept[d] ? 1 : 0, own[d] = ((axes >> d) & 1) ? 1 : mbnx[d];
+  if (artemis_hip_reduce_fields_level && artemis_hip_reduce_fields_level_work_bytes) {
+    const artemis_pack_t p = make_pack(base);
+    const int nsel = static_cast<int>(codes.size());
+    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
+    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
+    const int zero = 0;
+    const size_t work1 = artemis_hip_reduce_fields_level_work_bytes(&p, 0, 1, nsel, codes.data(), single ? 1 : 0, axes, &zero); // (linear in the blocks, whatever their shifts)
+    for (int b0 = 0; b0 < nb;) {
+      int n = 1; // as many blocks as the cap holds in output and in work, one where a block is larger
+      while (b0 + n < nb && static_cast<size_t>(off[b0 + n + 1] - off[b0]) * esz <= cap && static_cast<size_t>(n + 1) * work1 <= cap) ++n;
+      const size_t bytes = static_cast<size_t>(off[b0 + n] - off[b0]) * esz;
+      const size_t need = (bytes + sizeof(double) - 1) / sizeof(double), wneed = static_cast<size_t>(n) * work1 / sizeof(double);
+      if (field_stage.n < need) field_stage.alloc(need);
+      if (field_work.n < wneed) field_work.alloc(wneed);
+      CK(artemis_hip_reduce_fields_level(&p, b0, n, nsel, codes.data(), single ? 1 : 0, axes, shift.data() + b0, field_stage.p, field_work.p, stream),
+         "reduce fields level");
+      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(off[b0]) * esz, field_stage.p, bytes, stream), "d2h");
+      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffers)
+      b0 += n;
+    }
+    return total;
+  }
+  std::vector<Real> cur, nxt;
+  for (int b = 0; b < nb; ++b) {
+    const int s = shift[b], r = s < 0 ? -s : s;
+    host_reduce_block(b, codes, comp0, ncomp, axes, cur);
+    int n[3] = {own[0], own[1], own[2]};
+    if (s > 0) {
+      for (int d = 0; d < 3; ++d) { // x = x[0::2] + x[1::2] along each kept direction, s times
+        if (!kept[d]) continue;
+        for (int t = 0; t < s; ++t) {
+          const size_t inner = d == 0 ? 1 : (d == 1 ? n[0] : static_cast<size_t>(n[0]) * n[1]), half = static_cast<size_t>(n[d]) / 2;
+          const size_t rows = cur.size() / (static_cast<size_t>(n[d]) * inner);
+          nxt.assign(rows * half * inner, 0.0);
+          for (size_t row = 0; row < rows; ++row)
+            for (size_t h = 0; h < half; ++h)
+              for (size_t x = 0; x < inner; ++x)
+                nxt[(row * half + h) * inner + x] = cur[(row * 2 * half + 2 * h) * inner + x] + cur[(row * 2 * half + 2 * h + 1) * inner + x];
+          cur.swap(nxt);
+          n[d] = static_cast<int>(half);
+        }
+      }
+    } else if (s < 0) {
+      const Real share = std::ldexp(1.0, -r * m); // 2^(-|s| m): an exact scaling
+      const int rs[3] = {kept[0] ? r : 0, kept[1] ? r : 0, kept[2] ? r : 0};
+      const int o[3] = {n[0] << rs[0], n[1] << rs[1], n[2] << rs[2]};
+      const size_t zi = static_cast<size_t>(n[0]) * n[1] * n[2], zo = static_cast<size_t>(o[0]) * o[1] * o[2];
+      nxt.assign((static_cast<size_t>(ncomp) + 1) * zo, 0.0);
+      for (int c = 0; c <= ncomp; ++c)
+        for (int k = 0; k < o[2]; ++k)
+          for (int j = 0; j < o[1]; ++j)
+            for (int i = 0; i < o[0]; ++i) {
+              const Real x = cur[c * zi + (static_cast<size_t>(k >> rs[2]) * n[1] + (j >> rs[1])) * n[0] + (i >> rs[0])];
+              nxt[c * zo + (static_cast<size_t>(k) * o[1] + j) * o[0] + i] = m > 0 ? x * share : x;
+            }
+      cur.swap(nxt);
+    }
+    if (static_cast<long>(cur.size()) != off[b + 1] - off[b]) throw std::runtime_error("reduced fields at a level: size mismatch");
+    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(off[b]) * esz;
     for (size_t e = 0; e < cur.size(); ++e) {
       if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(cur[e]);
       else reinterpret_cast<double *>(ob)[e] = cur[e];
@@ -4419,6 +4540,10 @@ size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bo
 size_t gather_fields_reduced(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, void *host_out) {
   return sim->p->gather_fields_reduced(codes, single, axes, host_out);
 }
+size_t gather_fields_reduced_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, int level, void *host_out,
+                                   long *offsets) {
+  return sim->p->gather_fields_reduced_level(codes, single, axes, level, host_out, offsets);
+}
 FieldsLayout fields_layout(artemis_sim_t *sim) {
   const artemis_sim_impl &S = *sim->p;
   static const char *const names[6] = {"cartesian", "cylindrical", "spherical1D", "spherical2D", "spherical3D", "axisymmetric"};
@@ -4769,6 +4894,31 @@ long artemis_sim_gather_fields_reduced(artemis_sim_t *s, int nvar, const char *c
       ncomp += n;
     }
     const size_t bytes = s->p->gather_fields_reduced(codes, single != 0, axes, host_out);
+    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
+  };
+  GUARD(gather(), return -1)
+  return ret;
+}
+long artemis_sim_gather_fields_reduced_level(artemis_sim_t *s, int nvar, const char *const *names, int single, int axes, int level,
+                                             void *host_out, long *block_offsets) {
+  long ret = -1;
+  if (!s->dead.empty()) {
+    g_sim_err = s->dead;
+    return -1;
+  }
+  auto gather = [&]() {
+    const artemis_out::Clock c = artemis_out::clock_of(s);
+    std::vector<int> codes;
+    int ncomp = 0;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = artemis_out::field_var_code(name);
+      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
+      if (n == 0) throw std::runtime_error("gather_fields_reduced_level: unknown variable " + name);
+      codes.push_back(code);
+      ncomp += n;
+    }
+    const size_t bytes = s->p->gather_fields_reduced_level(codes, single != 0, axes, level, host_out, block_offsets);
     ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
   };
   GUARD(gather(), return -1)

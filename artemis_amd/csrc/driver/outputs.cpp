@@ -47,6 +47,8 @@ struct OutBlock {
   bool has_level = false; // fld: `level = L`, every block resampled to the zone size of refinement level L (may be negative)
   int level = 0;
   int reduce = 0; // fld: `reduce = x2,x3`, the mask of the directions every block is integrated over (0: none)
+  bool has_reduce_level = false; // fld: `reduce_level = L` beside `reduce`: the kept directions brought to the zone size of level L
+  int reduce_level = 0;
   std::string skip;
 };
 
@@ -129,6 +131,19 @@ void parse_fld(artemis_host::ParameterInput &pin, const Clock &c, OutBlock &b) {
     std::string rule = reduce_parse(pin.GetString(b.name, "reduce"), b.reduce);
     if (rule.empty()) rule = reduce_rule(b.reduce, c.mbnx);
     if (rule.empty() && b.has_level) rule = "reduce: a block that also sets level is not built";
+    if (b.skip.empty() && !rule.empty()) b.skip = rule;
+  }
+  if (pin.DoesParameterExist(b.name, "reduce_level")) {
+    b.has_reduce_level = true, b.reduce_level = pin.GetInteger(b.name, "reduce_level");
+    std::string rule;
+    if (b.has_level) rule = "reduce_level: a block that also sets level is not built";
+    else if (!pin.DoesParameterExist(b.name, "reduce")) rule = "reduce_level: only valid beside reduce";
+    // the worst shifts this deck can ever produce: its finest possible level and the root grid
+    for (const int lv : {c.finest_level, 0}) {
+      if (!rule.empty() || !b.skip.empty()) break;
+      const std::string bad = reduce_level_rule(lv - b.reduce_level, b.reduce, c.mbnx);
+      if (!bad.empty()) rule = "reduce_level " + std::to_string(b.reduce_level) + ": a block on level " + std::to_string(lv) + " " + bad;
+    }
     if (b.skip.empty() && !rule.empty()) b.skip = rule;
   }
   if (!b.skip.empty()) b.kind = SKIPPED;
@@ -255,11 +270,14 @@ void write_file(const std::string &name, const void *data, size_t bytes) {
 // reduce == 0 and level = null: version 1.
 // reduce == 0 and a level: version 2 -- "level", and every block entry carries the nx it was written with and the element
 // offset of its first value in its rank's part (the blocks of a rank follow each other in index order).
-std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single, const int *level, int reduce) {
+// reduce != 0 and a reduce_level: version 4 -- version 3 with "reduce_level", every block entry carrying the nx it was
+// brought to along the kept directions and, as in version 2, its element offset in its rank's part.
+std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single, const int *level, int reduce,
+                      const int *reduce_level = nullptr) {
   std::string red;
   for (int d = 0; d < 3; ++d)
     if ((reduce >> d) & 1) red += std::string(red.empty() ? "" : ", ") + "\"x" + std::to_string(d + 1) + "\"";
-  std::string j = std::string("{\"format\": \"artemis_fld\", \"version\": ") + (reduce ? "3, \"reduce\": [" + red + "]" : level ? "2, \"level\": " + std::to_string(*level) : std::string("1")) +
+  std::string j = std::string("{\"format\": \"artemis_fld\", \"version\": ") + (reduce && reduce_level ? "4, \"reduce\": [" + red + "], \"reduce_level\": " + std::to_string(*reduce_level) : reduce ? "3, \"reduce\": [" + red + "]" : level ? "2, \"level\": " + std::to_string(*level) : std::string("1")) +
                   ", \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
                   ", \"cycle\": " + std::to_string(c.ncycle) + ", \"coordinates\": " + json_str(L.coordinates) +
                   ", \"ndim\": " + std::to_string(L.ndim) + ", \"nghost\": 0, \"dtype\": " + (single ? "\"<f4\"" : "\"<f8\"") +
@@ -295,6 +313,24 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
       }
     }
   }
+  if (reduce && reduce_level) {
+    std::vector<std::vector<size_t>> of_rank(static_cast<size_t>(L.nranks));
+    for (size_t g = 0; g < L.blocks.size(); ++g) of_rank[static_cast<size_t>(L.blocks[g].rank)].push_back(g);
+    auto extent = [&](size_t g, int d) { return reduce_level_extent(L.nx[d], L.blocks[g].level - *reduce_level, reduce, d); };
+    for (std::vector<size_t> &gs : of_rank) {
+      std::sort(gs.begin(), gs.end(), [&](size_t a, size_t b) { return L.blocks[a].index < L.blocks[b].index; });
+      long at = 0;
+      for (const size_t g : gs) offset[g] = at, at += static_cast<long>(ncomp + 1) * extent(g, 0) * extent(g, 1) * extent(g, 2);
+    }
+    for (size_t g = 0; g < L.blocks.size(); ++g) {
+      const FieldBlock &B = L.blocks[g];
+      j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
+      for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
+      j += "], \"nx\": [" + std::to_string(extent(g, 0)) + ", " + std::to_string(extent(g, 1)) + ", " + std::to_string(extent(g, 2)) +
+           "], \"offset\": " + std::to_string(offset[g]) + ", \"rank\": " + std::to_string(B.rank) + ", \"index\": " + std::to_string(B.index) + "}";
+    }
+    return j + "]}\n";
+  }
   if (reduce) {
     const int o[3] = {(reduce & 1) ? 1 : L.nx[0], (reduce & 2) ? 1 : L.nx[1], (reduce & 4) ? 1 : L.nx[2]};
     for (size_t g = 0; g < L.blocks.size(); ++g) {
@@ -328,7 +364,7 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
 // One field dump (artemis_driver.h: artemis_sim_write_fields).  Every rank takes every vote, whatever happened to it
 // before: the votes are collective.
 void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single, const int *level = nullptr,
-                  int reduce = 0) {
+                  int reduce = 0, const int *reduce_level = nullptr) {
   std::string err, dir = path_in, tmp;
   while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
   tmp = dir + ".tmp";
@@ -349,10 +385,12 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   bool failed = vote(sim, !err.empty());
   if (!failed) {
     try {
-      std::vector<char> host(reduce  ? gather_fields_reduced(sim, codes, single, reduce, nullptr)
+      std::vector<char> host(reduce && reduce_level ? gather_fields_reduced_level(sim, codes, single, reduce, *reduce_level, nullptr, nullptr)
+                             : reduce ? gather_fields_reduced(sim, codes, single, reduce, nullptr)
                              : level ? gather_fields_level(sim, codes, single, *level, nullptr, nullptr)
                                      : gather_fields(sim, codes, single, nullptr));
-      if (reduce) gather_fields_reduced(sim, codes, single, reduce, host.data());
+      if (reduce && reduce_level) gather_fields_reduced_level(sim, codes, single, reduce, *reduce_level, host.data(), nullptr);
+      else if (reduce) gather_fields_reduced(sim, codes, single, reduce, host.data());
       else if (level) gather_fields_level(sim, codes, single, *level, host.data(), nullptr);
       else gather_fields(sim, codes, single, host.data());
       write_file(tmp + "/rank" + std::to_string(c.rank) + ".bin", host.data(), host.size());
@@ -364,7 +402,7 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   if (!failed) {
     try {
       if (c.rank == 0) {
-        const std::string meta = meta_json(c, L, codes, single, level, reduce);
+        const std::string meta = meta_json(c, L, codes, single, level, reduce, reduce_level);
         write_file(tmp + "/meta.json", meta.data(), meta.size()); // last: a directory with it has all its parts
         remove_field_dir(dir);
         if (std::rename(tmp.c_str(), dir.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + dir + ": " + std::strerror(errno));
@@ -388,7 +426,7 @@ void write_field_dump(artemis_sim_t *sim, State &st, OutBlock &b, bool final) {
   char num[16];
   std::snprintf(num, sizeof num, "%05ld", b.counter);
   b.path = st.dir + "/" + st.problem_id + ".out" + std::to_string(b.index) + "." + (final ? std::string("final") : std::string(num)) + ".fld";
-  write_fields(sim, b.path, b.codes, b.single, b.has_level ? &b.level : nullptr, b.reduce);
+  write_fields(sim, b.path, b.codes, b.single, b.has_level ? &b.level : nullptr, b.reduce, b.has_reduce_level ? &b.reduce_level : nullptr);
   if (!final) b.counter++;
 }
 
@@ -538,6 +576,30 @@ int artemis_sim_write_fields_reduced(artemis_sim_t *sim, const char *path, int n
   }
 }
 
+int artemis_sim_write_fields_reduced_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes,
+                                           int level) {
+  using namespace artemis_out;
+  try {
+    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
+    const Clock c = clock_of(sim);
+    std::vector<int> codes;
+    for (int v = 0; v < nvar; ++v) {
+      const std::string name = (names && names[v]) ? names[v] : "";
+      const int code = field_var_code(name);
+      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
+      codes.push_back(code);
+    }
+    const std::string rule = reduce_rule(axes, c.mbnx); // (every rank holds blocks of the same shape: all refuse or none)
+    if (!rule.empty()) throw std::runtime_error("write_fields: " + rule);
+    // (a shift that breaks a rule throws inside the gather, on the ranks that hold such a block, and the vote spreads it)
+    write_fields(sim, path, codes, single != 0, nullptr, axes, &level);
+    return 0;
+  } catch (const std::exception &e) {
+    artemis_ckpt::set_error(e.what());
+    return 1;
+  }
+}
+
 long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in, double time) {
   using namespace artemis_out;
   try {
@@ -589,6 +651,7 @@ int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long 
             if ((b.reduce >> d) & 1) j += std::string(n++ ? ", " : "") + "\"x" + std::to_string(d + 1) + "\"";
           j += "]";
         }
+        if (b.has_reduce_level) j += ", \"reduce_level\": " + std::to_string(b.reduce_level);
       }
       j += "}";
     }

@@ -112,6 +112,20 @@ inline std::string reduce_rule(int axes, const int nx[3]) {
 // (driver.cpp) the gather with every block integrated over `axes`: [local block][component, the volume last][nk'][nj'][ni']
 // with the reduced extents 1.  host_out = NULL: the size only.  Throws, before anything is written, where reduce_rule does.
 size_t gather_fields_reduced(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, void *host_out);
+// ---- ... and brought to a refinement level along the KEPT directions (active, outside axes): artemis_hip.h,
+// artemis_hip_reduce_fields_level, has the definition.  A reduced extent is 1 at every shift.
+inline int reduce_level_extent(int n, int shift, int axes, int d) { return ((axes >> d) & 1) ? 1 : level_extent(n, shift); }
+// "" or the rule a block of nx zones breaks at this shift with these axes: level_rule on the kept extents
+inline std::string reduce_level_rule(int shift, int axes, const int nx[3]) {
+  const int kept[3] = {(axes & 1) ? 1 : nx[0], (axes & 2) ? 1 : nx[1], (axes & 4) ? 1 : nx[2]};
+  return level_rule(shift, kept);
+}
+// (driver.cpp) the reduced gather with every block on the zone size of `level` along the kept directions, the blocks one
+// after the other, each [component, the volume last][nk'][nj'][ni']; offsets (nblocks_local + 1 longs, or null): element
+// offset of every block and the total.  host_out = NULL: sizes only.  Throws, before anything is written, where
+// reduce_rule or -- for any block -- reduce_level_rule does.
+size_t gather_fields_reduced_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, int level, void *host_out,
+                                   long *offsets);
 // (driver.cpp) the inverse: host_in in that layout, holding one complete form of the state per fluid (csrc/fields_form.hpp),
 // becomes the interior primitives of the current buffer -- artemis_hip_unpack_fields out of the same staging buffer, or the
 // host loop -- and the state is completed as a problem generator's is; time = NaN keeps the clock, dt is estimated afresh.

@@ -164,6 +164,15 @@ void launch_pack_fields_level(const PackView &P, int block0, int nblocks, const 
 long reduce_fields_work_elements(const int nx[3], int nblocks, int ncomp, int axes);
 void launch_reduce_fields(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, int axes, void *out, double *work,
                           hipStream_t s);
+// ... brought to a chosen refinement level along the KEPT directions (active and not in `axes`): block b has shift[b] = its
+// level - the level asked for, |shift| <= FIELDS_MAX_SHIFT; off[b]: element offset of block block0 + b in `out`
+// (artemis_hip.h, artemis_hip_reduce_fields_level, has the definition).  `work`: reduce_fields_level_work_elements doubles.
+inline int reduce_level_extent(int n, int shift, int axes, int d) {
+  return ((axes >> d) & 1) ? 1 : level_extent(n, shift);
+}
+long reduce_fields_level_work_elements(const int nx[3], int nblocks, int ncomp, int axes);
+void launch_reduce_fields_level(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, int axes, const int *shift,
+                                const long *off, void *out, double *work, hipStream_t s);
 // ... and its inverse: the form of each fluid that the buffer holds (fields_form.hpp) written to the interior primitives
 void launch_unpack_fields(const PackView &P, int block0, int nblocks, const FieldUnpack &U, bool single, const void *in, hipStream_t s);
 } // namespace artemis

@@ -174,6 +174,103 @@ __global__ __launch_bounds__(256) void reduce_axis_kernel(const double *in, long
   }
 }
 
+// ---- reduced output on a chosen level (artemis_hip_reduce_fields_level) -------------------------------------------------
+// The passes above leave every block of the range as doubles [ncomp + 1][n3][n2][n1] in the work buffer, the reduced
+// extents 1.  resample_reduced_kernel brings block q to its shift s along the KEPT directions (active and not reduced; at
+// most two, A before B in the order x1, x2, x3) and narrows at this one store:
+//   s >= 1   out = the pair tree x[0::2] + x[1::2], s times along A, then s times along B: the thread reads its 2^s values
+//            along A (all loads of a row issued ahead of its additions), adds them as the tree, and does so for each of
+//            its 2^s rows along B, whose results go up the same tree.  Plain additions.
+//   s == 0   a copy.
+//   s <= -1  out(k, j, i) = x(k >> |s|, j >> |s|, i >> |s|) * 2^(-|s| m) along the kept directions, m their number: one load,
+//            one exact multiply (a power of two), one store; m = 0: no multiply at all.
+// One thread per OUTPUT element, consecutive lanes on consecutive elements of a block's output -- the first kept direction
+// is the fastest one -- 256 to a tile, the tiles of the launch's blocks one after the other (tile0) and taken by grid
+// stride; lanes past a block's last element store nothing.  The blocks of a launch are consecutive blocks of the range
+// and may differ in shift: shift, output offset and first tile travel by value (no table to upload).  No LDS, no atomics,
+// vector stores, 64-bit offsets.
+constexpr int RESAMPLE_MAX_BLOCKS = 192;
+struct ResampleBlocks {
+  int n, q0;                          // blocks of this launch, the first one's place in the range
+  int tile0[RESAMPLE_MAX_BLOCKS + 1]; // first tile of every block, and the number of tiles
+  long off[RESAMPLE_MAX_BLOCKS];      // element offset of the block's first value in the output
+  signed char shift[RESAMPLE_MAX_BLOCKS];
+};
+struct ResampleShape {
+  int n[3], kept[3]; // extents the passes left (1 where reduced); 1 where the direction is kept
+  int rows, m;       // ncomp + 1; kept directions
+};
+static_assert(sizeof(ResampleBlocks) + sizeof(ResampleShape) + 64 <= 4096, "kernel arguments");
+
+template <int S>
+__device__ __forceinline__ double pair_tree(double (&v)[1 << S]) {
+  static_for<S>([&](auto mm) {
+    constexpr int half = 1 << (S - 1 - decltype(mm)::value);
+#pragma unroll
+    for (int l = 0; l < half; ++l) v[l] = v[2 * l] + v[2 * l + 1];
+  });
+  return v[0];
+}
+// x: the first of the 2^S (A) x 2^S (B) inputs of one output element; a direction that is not there has stride 0 and one value
+template <int S>
+__device__ __forceinline__ double restrict_pairs(const double *x, bool hasA, long sA, bool hasB, long sB) {
+  constexpr int R = 1 << S;
+  double b[R];
+#pragma unroll
+  for (int tb = 0; tb < R; ++tb) {
+    b[tb] = 0.0;
+    if (tb == 0 || hasB) {
+      double a[R];
+#pragma unroll
+      for (int ta = 0; ta < R; ++ta) a[ta] = (ta == 0 || hasA) ? x[tb * sB + ta * sA] : 0.0; // (issued ahead of the additions)
+      b[tb] = hasA ? pair_tree<S>(a) : a[0];
+    }
+  }
+  return hasB ? pair_tree<S>(b) : b[0];
+}
+
+template <class OUT>
+__global__ __launch_bounds__(256) void resample_reduced_kernel(const double *in, const ResampleShape H, const ResampleBlocks B, OUT *out) {
+  const long zin = static_cast<long>(H.n[0]) * H.n[1] * H.n[2];
+  const long stride[3] = {1, H.n[0], static_cast<long>(H.n[0]) * H.n[1]};
+  for (long tile = blockIdx.x; tile < B.tile0[B.n]; tile += gridDim.x) {
+    int q = 0, hi = B.n; // the block of this tile: the last one with tile0 <= tile (uniform over the workgroup)
+    while (hi - q > 1) {
+      const int mid = (q + hi) >> 1;
+      if (B.tile0[mid] <= tile) q = mid;
+      else hi = mid;
+    }
+    const int s = B.shift[q], r = s < 0 ? -s : s;
+    int o[3];
+    for (int d = 0; d < 3; ++d) o[d] = !H.kept[d] ? H.n[d] : (s >= 0 ? H.n[d] >> r : H.n[d] << r);
+    const long oz = static_cast<long>(o[0]) * o[1] * o[2];
+    const long e = (tile - B.tile0[q]) * 256 + threadIdx.x;
+    if (e >= H.rows * oz) continue;
+    const long c = e / oz, z = e % oz;
+    const int io[3] = {static_cast<int>(z % o[0]), static_cast<int>((z / o[0]) % o[1]), static_cast<int>(z / (static_cast<long>(o[0]) * o[1]))};
+    long at = ((static_cast<long>(B.q0) + q) * H.rows + c) * zin; // the input element this one starts from
+    bool hasA = false, hasB = false;
+    long sA = 0, sB = 0;
+    for (int d = 0; d < 3; ++d) {
+      at += stride[d] * (!H.kept[d] ? io[d] : (s >= 0 ? static_cast<long>(io[d]) << r : io[d] >> r));
+      if (H.kept[d]) {
+        if (!hasA) hasA = true, sA = stride[d];
+        else hasB = true, sB = stride[d];
+      }
+    }
+    const double *x = in + at;
+    double v;
+    if (s == 1) v = restrict_pairs<1>(x, hasA, sA, hasB, sB);
+    else if (s == 2) v = restrict_pairs<2>(x, hasA, sA, hasB, sB);
+    else if (s == 3) v = restrict_pairs<3>(x, hasA, sA, hasB, sB);
+    else {
+      v = x[0];
+      if (s < 0 && H.m > 0) v = v * __hiloint2double((1023 - r * H.m) << 20, 0); // 2^(-|s| m), exact
+    }
+    put(out, B.off[q] + e, v);
+  }
+}
+
 template <class SL>
 unsigned slot_mask(const FieldSelection &F) {
   unsigned m = 1u << (SL::NV - 1);
@@ -250,6 +347,53 @@ void launch_reduce_fields(const PackView &P, int block0, int nblocks, const Fiel
     }
     in = w, work = w + rows0 * n[0] * n[1] * n[2];
   }
+}
+
+// doubles of work artemis_hip_reduce_fields_level takes: the blocks reduced at their own resolution, then what those passes need
+long reduce_fields_level_work_elements(const int nx[3], int nblocks, int ncomp, int axes) {
+  long own = static_cast<long>(nblocks) * (ncomp + 1);
+  for (int d = 0; d < 3; ++d)
+    if (!((axes >> d) & 1)) own *= nx[d];
+  return own + reduce_fields_work_elements(nx, nblocks, ncomp, axes);
+}
+
+// The caller has checked axes, selection and shifts (|shift| <= 3, kept extents divisible by 2^shift); off[b]: element offset
+// of block block0 + b in `out`.  The existing passes run unchanged with double output into the head of `work`; one resample
+// launch per RESAMPLE_MAX_BLOCKS consecutive blocks follows on the same stream.
+void launch_reduce_fields_level(const PackView &P, int block0, int nblocks, const FieldSelection &F, bool single, int axes, const int *shift,
+                                const long *off, void *out, double *work, hipStream_t s) {
+  if (nblocks == 0 || F.ncomp == 0) return;
+  ResampleShape H;
+  const int nx[3] = {P.ie - P.is + 1, P.je - P.js + 1, P.ke - P.ks + 1};
+  H.rows = F.ncomp + 1, H.m = 0;
+  long zin = 1;
+  for (int d = 0; d < 3; ++d) {
+    H.n[d] = ((axes >> d) & 1) ? 1 : nx[d];
+    H.kept[d] = (!((axes >> d) & 1) && nx[d] > 1) ? 1 : 0;
+    H.m += H.kept[d], zin *= H.n[d];
+  }
+  const long own = static_cast<long>(nblocks) * H.rows * zin;
+  launch_reduce_fields(P, block0, nblocks, F, false, axes, work, work + own, s);
+  ResampleBlocks B;
+  B.n = 0, B.q0 = 0, B.tile0[0] = 0;
+  auto flush = [&]() {
+    if (B.n == 0) return;
+    const long wg = B.tile0[B.n];
+    const dim3 g(static_cast<unsigned>(grid_capped(wg < REDUCE_MAX_WG ? wg : REDUCE_MAX_WG)));
+    if (single) hipLaunchKernelGGL((resample_reduced_kernel<float>), g, dim3(256), 0, s, work, H, B, static_cast<float *>(out));
+    else hipLaunchKernelGGL((resample_reduced_kernel<double>), g, dim3(256), 0, s, work, H, B, static_cast<double *>(out));
+    B.n = 0;
+  };
+  for (int b = 0; b < nblocks; ++b) {
+    long oz = 1;
+    for (int d = 0; d < 3; ++d) oz *= H.kept[d] ? (shift[b] >= 0 ? H.n[d] >> shift[b] : H.n[d] << -shift[b]) : H.n[d];
+    const long tiles = (H.rows * oz + 255) / 256;
+    if (B.n == RESAMPLE_MAX_BLOCKS || (B.n > 0 && B.tile0[B.n] + tiles > (1L << 30))) flush(); // (tile0 is an int)
+    if (B.n == 0) B.q0 = b;
+    B.shift[B.n] = static_cast<signed char>(shift[b]), B.off[B.n] = off[b];
+    B.tile0[B.n + 1] = static_cast<int>(B.tile0[B.n] + tiles), B.n++;
+  }
+  flush();
 }
 
 } // namespace artemis

@@ -264,6 +264,9 @@ def _declare(L):
     L.artemis_sim_gather_fields_reduced.restype = l
     L.artemis_sim_gather_fields_reduced.argtypes = [vp, i, C.POINTER(C.c_char_p), i, i, vp]
     L.artemis_sim_write_fields_reduced.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i, i]
+    L.artemis_sim_gather_fields_reduced_level.restype = l
+    L.artemis_sim_gather_fields_reduced_level.argtypes = [vp, i, C.POINTER(C.c_char_p), i, i, i, vp, C.POINTER(l)]
+    L.artemis_sim_write_fields_reduced_level.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i, i, i]
     L.artemis_sim_scatter_fields.restype = l
     L.artemis_sim_scatter_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp, d]
     L._sim_declared = True
@@ -528,7 +531,18 @@ class Simulation:
             raise ValueError("reduce names no direction")
         return axes
 
-    def gather(self, variables, single=False, level=None, reduce=None):
+    @staticmethod
+    def _reduce_level(reduce, level, reduce_level):
+        """reduce_level as an int, or None; it is only valid beside reduce and never with level"""
+        if reduce_level is None:
+            return None
+        if reduce is None:
+            raise ValueError("reduce_level is only valid beside reduce")
+        if level is not None:
+            raise ValueError("reduce_level together with level is not built: level resamples means, reduce_level integrals")
+        return int(reduce_level)
+
+    def gather(self, variables, single=False, level=None, reduce=None, reduce_level=None):
         """The named variables ('gas.prim.density', 'gas.prim.velocity', 'gas.prim.pressure', ...: include/artemis_driver.h
         "field output") of this rank's blocks, interior zones only, as [nblocks_local, ncomp, nz, ny, nx] float64 (float32
         with single=True).  Formed from the primitives on the device; nothing is materialised and the run is not disturbed.
@@ -540,8 +554,33 @@ class Simulation:
         on the device -- per component the sum of V q, and the sum of the volumes V as one more, last, component -- and
         returned as [nblocks_local, ncomp + 1, nz', ny', nx'] with the reduced extents 1.  The order of the additions is
         fixed (include/artemis_hip.h, artemis_hip_reduce_fields), so the bits depend on the block alone; a mean is N / W
-        after the blocks that share an output cell have been added.  reduce with level raises ValueError."""
+        after the blocks that share an output cell have been added.  reduce with level raises ValueError.
+        reduce_level = an int (beside reduce): every reduced block also brought, on the device, to the zone size of refinement
+        level `reduce_level` along the directions it keeps -- finer blocks by adding pairs, coarser ones by an equal share of
+        N and W for each output cell under a coarse zone (include/artemis_hip.h, artemis_hip_reduce_fields_level) -- and
+        returned as a list, in local block order, of [ncomp + 1, nz_b, ny_b, nx_b] views of one buffer, the volume last.
+        All blocks then share a zone size, so those of a refined mesh add cell by cell.  reduce_level without reduce, or
+        with level, raises ValueError."""
         names, n = self._names(variables)
+        rl = self._reduce_level(reduce, level, reduce_level)
+        if rl is not None:
+            axes = self._axes(reduce, level)
+            self._refresh_dims()
+            off = (C.c_long * (self.nblocks + 1))()
+            nbytes = self.L.artemis_sim_gather_fields_reduced_level(self.h, n, names, int(single), axes, rl, None, off)
+            if nbytes < 0:
+                raise RuntimeError(self.L.artemis_sim_last_error().decode())
+            out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
+            ncomp = self.L.artemis_sim_gather_fields_reduced_level(self.h, n, names, int(single), axes, rl, out.ctypes.data, off)
+            if ncomp < 0:
+                raise RuntimeError(self.L.artemis_sim_last_error().decode())
+            nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
+            blocks = []
+            for b in range(self.nblocks):
+                s = self.block_level(b) - rl
+                shape = [1 if (axes >> q) & 1 or m == 1 else (m >> s if s >= 0 else m << -s) for q, m in enumerate(nx)]
+                blocks.append(out[off[b]:off[b + 1]].reshape(ncomp + 1, shape[2], shape[1], shape[0]))
+            return blocks
         if reduce is not None:
             axes = self._axes(reduce, level)
             nbytes = self.L.artemis_sim_gather_fields_reduced(self.h, n, names, int(single), axes, None)
@@ -582,13 +621,19 @@ class Simulation:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
         return out.reshape(self.nblocks, ncomp, self.ke - self.ks + 1, self.je - self.js + 1, self.ie - self.is_ + 1)
 
-    def write_fields(self, path, variables, single=False, level=None, reduce=None):
+    def write_fields(self, path, variables, single=False, level=None, reduce=None, reduce_level=None):
         """One dump of the named variables as a directory at `path` (collective over the ranks of the run; replaces an
         existing one).  artemis_amd.fields.read_fields reads it.  level = an int: every block resampled to refinement level
         `level` as in gather (a version-2 dump; FieldDump.uniform() then works on any mesh).  reduce = ("x2", "x3"): every
-        block integrated over those directions as in gather (a version-3 dump; FieldDump.reduced() assembles it)."""
+        block integrated over those directions as in gather (a version-3 dump; FieldDump.reduced() assembles it).
+        reduce_level = an int beside reduce: the reduced blocks brought to that level along their kept directions as in gather
+        (a version-4 dump, which FieldDump.reduced() assembles on any mesh)."""
         names, n = self._names(variables)
-        if reduce is not None:
+        rl = self._reduce_level(reduce, level, reduce_level)
+        if rl is not None:
+            rc = self.L.artemis_sim_write_fields_reduced_level(self.h, os.fspath(path).encode(), n, names, int(single),
+                                                               self._axes(reduce, level), rl)
+        elif reduce is not None:
             rc = self.L.artemis_sim_write_fields_reduced(self.h, os.fspath(path).encode(), n, names, int(single), self._axes(reduce, level))
         elif level is None:
             rc = self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single))

@@ -7,19 +7,23 @@ over interior zones.  Version 1: every block has the zones of a mesh block.  Ver
 Version 3 (write_fields(reduce=("x2", "x3")), a deck's `reduce = x2,x3`): every block was integrated over those directions
 on the device -- per component N = sum of V q, and W = sum of V as the last variable, "volume" -- in an order of additions
 that depends on the block alone (include/artemis_hip.h, artemis_hip_reduce_fields); the reduced extents of every nx are 1.
-FieldDump.reduced() adds the blocks and forms the means.  Needs numpy only and no device."""
+FieldDump.reduced() adds the blocks and forms the means.  Version 4 (write_fields(reduce=..., reduce_level=L), a deck's
+`reduce_level = L` beside `reduce`): a version-3 dump whose blocks were also brought to the zone size of refinement level L
+along the directions they keep (include/artemis_hip.h, artemis_hip_reduce_fields_level) -- each entry carries its own nx and
+offset -- so reduced() assembles it on any mesh.  Needs numpy only and no device."""
 import json
 import os
 
 import numpy as np
 
-FORMAT, VERSIONS = "artemis_fld", (1, 2, 3)
+FORMAT, VERSIONS = "artemis_fld", (1, 2, 3, 4)
 
 
 class FieldDump:
     """time, dt, cycle, coordinates, ndim, gamma, dtype; variables: {name: number of components}; components: {name: their
     names}; blocks: [{gid, level, bounds, nx}] in gid order; level: None, or the level a version-2 dump was resampled to;
-    reduce: None, or the directions (["x2", "x3"]) a version-3 dump was integrated over."""
+    reduce: None, or the directions (["x2", "x3"]) a version-3 or version-4 dump was integrated over; reduce_level: None, or
+    the level the kept directions of a version-4 dump were brought to."""
 
     def __init__(self, path, meta):
         self.path, self.meta = path, meta
@@ -27,7 +31,8 @@ class FieldDump:
             setattr(self, k, meta[k])
         self.version = meta["version"]
         self.level = meta["level"] if self.version == 2 else None
-        self.reduce = list(meta["reduce"]) if self.version == 3 else None
+        self.reduce = list(meta["reduce"]) if self.version in (3, 4) else None
+        self.reduce_level = meta["reduce_level"] if self.version == 4 else None
         self.dtype = np.dtype(meta["dtype"])
         self.variables = {v["name"]: v["ncomp"] for v in meta["variables"]}
         self.components = {v["name"]: list(v["components"]) for v in meta["variables"]}
@@ -121,12 +126,18 @@ class FieldDump:
         return out
 
     def reduced(self, name, op=None):
-        """A version-3 dump assembled into one [ncomp, NZ, NY, NX] float64 array of the whole mesh, the reduced extents 1:
+        """A version-3 or version-4 dump assembled into one [ncomp, NZ, NY, NX] float64 array of the whole mesh, the reduced extents 1:
         every block is placed by its bounds in the kept directions, and blocks that meet the same output cell are added as
         float64 in gid order -- the first one assigned, each later one added -- both the integrals N and the volumes W.
         op = "integral": N; op = "mean": N / W, one division per cell.  gid order is global, so the bits do not depend on
         the number of ranks that wrote the dump.  On a mesh with several refinement levels the kept directions have no
-        common zone size: only a dump with every active direction reduced (scalars) is assembled, any other is refused.
+        common zone size in a version-3 dump: only one with every active direction reduced (scalars) is assembled, any other
+        is refused.  A version-4 dump (reduce_level) of any mesh is assembled: its blocks share the zone size of that level.
+        There each of the 2^(|s| m) cells under a block |s| levels coarser (m kept directions) received an EQUAL share of
+        that zone's N and W -- even in index space, not geometric.  op="mean" is exact on every mesh, each such cell holding
+        the coarse zone's own mean where no other block adds to it.  op="integral" of a single cell under a coarser block
+        is its even share: on a curvilinear mesh the sub-volumes of a coarse zone along a kept direction are not equal, so
+        only sums over the cells of whole coarse zones are exact there; on Cartesian meshes every cell is.
         name = "volume" returns W itself, [1, NZ, NY, NX]; it has no mean, so `op` must be "integral" or left at its default
         (ValueError for an explicit op="mean")."""
         if self.reduce is None:
@@ -139,7 +150,7 @@ class FieldDump:
         axes = {int(a[1]) - 1 for a in self.reduce}
         kept = [d for d in range(3) if d not in axes and self.nx[d] > 1]
         levels = sorted({b["level"] for b in self.blocks})
-        if len(levels) != 1 and kept:
+        if len(levels) != 1 and kept and self.reduce_level is None:
             raise ValueError("%s: blocks on levels %s kept along %s do not share a zone size: only a dump with every active "
                              "direction reduced is assembled on a refined mesh"
                              % (self.path, levels, ", ".join("x%d" % (d + 1) for d in kept)))

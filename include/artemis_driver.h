@@ -289,6 +289,28 @@ int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nva
  * as skipped with the reason ("reduce: ...") by artemis_sim_outputs_describe and writes nothing. */
 long artemis_sim_gather_fields_reduced(artemis_sim_t *sim, int nvar, const char *const *names, int single, int axes, void *host_out);
 int artemis_sim_write_fields_reduced(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes);
+/* ---- reduced field output on a chosen level: the same integrals with every block brought to the zone size of refinement
+ * level `level` (0 the root grid, negative coarser) along the directions it KEEPS (active and outside `axes`), so the blocks
+ * of a refined mesh add cell by cell.  A block on level l has shift s = l - level, |s| <= 3.  It is reduced at its own
+ * resolution exactly as above; s >= 1 then adds pairs, x = x[0::2] + x[1::2], s times along each kept direction (the kept
+ * extents must be divisible by 2^s); s <= -1 gives each of the 2^(|s| m) output cells under a coarse zone (m kept
+ * directions) an EQUAL share, N and W times 2^(-|s| m), so every covered cell has the coarse zone's own mean N / W bit for
+ * bit and the parts add back to the whole.  Nothing is split along a reduced direction.  The share is even in index space:
+ * on a curvilinear mesh the integral of a single output cell under a coarser block is its even share, not its geometric
+ * one; means, and sums over whole coarse zones, are exact (artemis_hip.h, artemis_hip_reduce_fields_level, has the
+ * definition).  Every shift is checked before anything is written.
+ *
+ * gather_reduced_level: host_out holds the local blocks one after the other, each [ncomp + 1][nk'][nj'][ni'], the volume
+ * last; block_offsets (nblocks_local + 1 longs, or NULL) receives the element offset of every block and the total.
+ * Returns the number of components WITHOUT the volume; with host_out = NULL the bytes needed.  < 0 on error.
+ * write_reduced_level: "version": 4 in meta.json -- version 3 plus "reduce_level", the block entries carrying the "nx"
+ * they were brought to and their "offset".  A deck's `reduce_level = L` beside `reduce` in a `fld` block writes these; it is
+ * checked at parse time against the worst shifts the deck can produce, and a block it cannot serve -- or one that sets
+ * reduce_level without reduce, or with `level` -- is listed as skipped with the reason ("reduce_level ..."). */
+long artemis_sim_gather_fields_reduced_level(artemis_sim_t *sim, int nvar, const char *const *names, int single, int axes, int level,
+                                             void *host_out, long *block_offsets);
+int artemis_sim_write_fields_reduced_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes,
+                                           int level);
 /* scatter: the inverse of gather -- the run takes its state from the caller's arrays, which is this driver's form of
  * "write your own problem generator".  host_in is this rank's blocks in local order, laid out as gather returns them for
  * the same names ([local block][component][nk][nj][ni] over the INTERIOR zones, double or float).  For each fluid the names

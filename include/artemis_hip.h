@@ -328,6 +328,41 @@ size_t artemis_hip_reduce_fields_work_bytes(const artemis_pack_t *p, int block0,
                                             int axes);
 int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
                               void *out_dev, void *work_dev, void *stream);
+/* Reduced field output ON A CHOSEN LEVEL: the same integrals with every block brought to one zone size along the directions
+ * it keeps, so the blocks of a refined mesh can be added cell by cell.  `axes` as above; shift_host[b] (HOST) is the shift
+ * s = (level of block block0 + b) - (level asked for), |s| <= 3.  `kept` are the ACTIVE directions (more than one zone)
+ * outside `axes`, m their number (0..2); an inactive direction is never halved, doubled or scaled.  Again the definition
+ * fixes the bits, not the launches (tests/fields_reduce_level_ref.py is its numpy form):
+ *   1. the block is reduced at its own resolution exactly as artemis_hip_reduce_fields defines it -- leaf, order, the x1
+ *      butterfly in chunks of 64, the x2 / x3 chains -- and N_c and W stay doubles.
+ *   2. s == 0: nothing more.  With every shift 0 the output is that of artemis_hip_reduce_fields bit for bit.
+ *   3. s >= 1 (the block is finer than the output): for each kept direction, in the order x1, x2, x3, x = x[0::2] + x[1::2]
+ *      along it, s times.  Plain additions, not fused; (-0.0) + (-0.0) stays -0.0.  Only the kept extents must be divisible by
+ *      2^s.  N and W are sums of the block's own V q and V, so this is exactly conservative and needs no geometry of a level
+ *      the pack does not hold.
+ *   4. s <= -1 (the block is coarser): nothing is split along a REDUCED direction -- the whole integral goes in.  Along the
+ *      kept directions a coarse zone covers 2^(|s| m) output cells and its N_c and W are shared among them EQUALLY: each is
+ *      multiplied by the double 2^(-|s| m), then out(k, j, i) = x(k >> |s|, j >> |s|, i >> |s|) along the kept directions.
+ *      The scaling is exact wherever the result is not subnormal; there the parts add back to the whole exactly, and the
+ *      mean N / W of every covered cell is the coarse zone's own mean bit for bit: no gradient is invented.  m == 0:
+ *      nothing is scaled or replicated.
+ *   5. stored per block as [ncomp + 1][nz'][ny'][nx'], W last, narrowed to float (single != 0) only at this store; the
+ *      device divides nothing and combines no blocks.
+ * The share of step 4 is even in INDEX space, not geometric: on a curvilinear mesh the sub-volumes of a coarse zone along a
+ * kept direction are not equal (the metric tables of a finer grid of that block do not exist on the device).  A mean is
+ * exact all the same; the integral of a single output cell under a coarser block is its even share, while sums over the
+ * cells of any whole coarse zone are exact.  On Cartesian meshes both are exact.
+ * work_dev (DEVICE, artemis_hip_reduce_fields_level_work_bytes, never 0 for a call that is taken) holds the doubles of step
+ * 1 and what its passes leave.  ARTEMIS_HIP_EINVAL, before anything is written, with block, shift and rule in
+ * artemis_hip_last_error(): |s| > 3; s >= 1 on a kept extent that 2^s does not divide; and everything
+ * artemis_hip_reduce_fields refuses.  Asynchronous on `stream`.  The two _bytes calls: the bytes these blocks take in
+ * out_dev / work_dev; 0 for arguments the call would refuse. */
+size_t artemis_hip_reduce_fields_level_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                                             const int *shift_host);
+size_t artemis_hip_reduce_fields_level_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
+                                                  int axes, const int *shift_host);
+int artemis_hip_reduce_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                                    const int *shift_host, void *out_dev, void *work_dev, void *stream);
 /* The inverse: in_dev (DEVICE) holds what artemis_hip_pack_fields writes for the same arguments -- [block - block0]
  * [component][k][j][i] over the interior zones, the components in the order of the codes of `sel`, double or (single != 0)
  * float, widened exactly -- and the PRIMITIVES of the interior zones of blocks [block0, block0 + nblocks) are written from
