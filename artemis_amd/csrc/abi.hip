@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "fields_shape.hpp"
 #include "options.hpp"
 #include "geometry_core.hpp"
 
@@ -275,192 +276,122 @@ static const char *field_selection(const artemis_pack_t *p, int nsel, const int 
   S.nsel = nsel;
   return "";
 }
+// The four field-output entry points make two choices -- integrate over axes or not, bring every block to a shift or not
+// -- and say who they are in their errors
+struct FieldsMode {
+  const char *who;
+  bool axes, level;
+};
+static const FieldsMode PACK_FIELDS = {"pack fields", false, false}, PACK_FIELDS_LEVEL = {"pack fields level", false, true},
+                        REDUCE_FIELDS = {"reduce fields", true, false}, REDUCE_FIELDS_LEVEL = {"reduce fields level", true, true};
+struct FieldsPlan {
+  artemis::FieldSelection F;
+  std::vector<long> off; // element offset of every block of the range in the output, off[nblocks]: the total
+  long work = 0;         // doubles of work the launch needs
+  bool empty = false;    // nothing to launch: an empty range, or PACK_FIELDS of no variables
+};
+// One validation for an entry point and its _bytes / _work_bytes companions: "" and the plan, or what is wrong -- checked
+// in the order selection, no variables, block range, primitive tables, axes, shifts.  launch = false (the size queries,
+// which answer 0 to every error): the pack itself is checked here, and the tables a launch would read are not asked for.
+static std::string fields_plan(const FieldsMode &M, const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int axes,
+                               const int *shift, bool launch, FieldsPlan &P) {
+  const std::string who = std::string(M.who) + ": ";
+  if (!launch && (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0))
+    return who + "no pack";
+  const char *bad = field_selection(p, nsel, sel, P.F);
+  if (*bad) return bad;
+  if ((M.axes || M.level) && nsel == 0) return who + "no variables";
+  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
+    return who + "blocks [" + std::to_string(block0) + ", " + std::to_string(block0) + " + " + std::to_string(nblocks) +
+           ") are not inside the pack's " + std::to_string(p->nblocks);
+  if (launch && ((P.F.want_gas && !p->gas.prim) || (P.F.want_dust && !p->dust.prim)))
+    return who + "the primitive tables of the fluids asked for are required";
+  const int nx[3] = {p->nx1, p->nx2, p->nx3};
+  if (M.axes) {
+    const std::string rule = artemis_fields::axes_rule(axes, nx, "axes = " + std::to_string(axes) + ", a non-empty mask of x1 (1), x2 (2), x3 (4) is taken");
+    if (!rule.empty()) return "reduce fields: " + rule;
+  }
+  P.off.assign(1, 0);
+  P.empty = nblocks == 0 || P.F.ncomp == 0;
+  if (P.empty) return "";
+  if (M.level && !shift) return who + "null shift_host";
+  int b = 0;
+  const std::string rule = artemis_fields::block_offsets(nx, P.F.ncomp + (M.axes ? 1 : 0), M.axes ? axes : 0, nblocks, M.level ? shift : nullptr, P.off,
+                                                         b, M.axes ? "kept nx" : "nx");
+  if (!rule.empty()) return who + "block " + std::to_string(block0 + b) + " has " + rule;
+  if (M.axes) P.work = M.level ? artemis::reduce_fields_level_work_elements(nx, nblocks, P.F.ncomp, axes)
+                               : artemis::reduce_fields_work_elements(nx, nblocks, P.F.ncomp, axes);
+  return "";
+}
+// ... of a size query: the bytes of output (work = false) or of work of the range, 0 for every error
+static size_t fields_bytes(const FieldsMode &M, const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
+                           const int *shift, bool work) {
+  FieldsPlan P;
+  if (!fields_plan(M, p, block0, nblocks, nsel, sel, axes, shift, false, P).empty()) return 0;
+  return work ? static_cast<size_t>(P.work) * sizeof(double) : static_cast<size_t>(P.off.back()) * (single ? sizeof(float) : sizeof(double));
+}
+// ... of a launch: 0 and the plan, P.empty where there is nothing to do, or the error as the entry point returns it
+static int fields_launch(const FieldsMode &M, const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int axes,
+                         const int *shift, const void *out_dev, const void *work_dev, FieldsPlan &P) {
+  if (int rc = validate(p)) return rc;
+  std::string bad = fields_plan(M, p, block0, nblocks, nsel, sel, axes, shift, true, P);
+  if (bad.empty() && !P.empty && !out_dev) bad = std::string(M.who) + ": null out_dev";
+  if (bad.empty() && !P.empty && !work_dev && P.work > 0) bad = std::string(M.who) + ": null work_dev";
+  return bad.empty() ? 0 : fail(ARTEMIS_HIP_EINVAL, "%s", bad.c_str());
+}
 size_t artemis_hip_pack_fields_bytes(const artemis_pack_t *p, int nsel, const int *sel, int single) {
-  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return 0;
-  artemis::FieldSelection S;
-  if (*field_selection(p, nsel, sel, S)) return 0;
-  return static_cast<size_t>(p->nblocks) * S.ncomp * p->nx1 * p->nx2 * p->nx3 * (single ? sizeof(float) : sizeof(double));
+  return fields_bytes(PACK_FIELDS, p, 0, p ? p->nblocks : 0, nsel, sel, single, 0, nullptr, false);
 }
 int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, void *out_dev,
                             void *stream) {
-  if (int rc = validate(p)) return rc;
-  artemis::FieldSelection F;
-  const char *bad = field_selection(p, nsel, sel, F);
-  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
-  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
-    return fail(ARTEMIS_HIP_EINVAL, "pack fields: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
-  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
-    return fail(ARTEMIS_HIP_EINVAL, "pack fields: the primitive tables of the fluids asked for are required");
-  if (nblocks == 0 || F.ncomp == 0) return 0;
-  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "pack fields: null out_dev");
-  artemis::launch_pack_fields(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, out_dev, S(stream));
+  FieldsPlan P;
+  if (int rc = fields_launch(PACK_FIELDS, p, block0, nblocks, nsel, sel, 0, nullptr, out_dev, nullptr, P)) return rc;
+  if (P.empty) return 0;
+  artemis::launch_pack_fields(artemis::make_pack_view(*p), block0, nblocks, P.F, single != 0, out_dev, S(stream));
   return after_launch("pack_fields");
-}
-// the shifts of artemis_hip_pack_fields_level: "" and the element offset of every block (off[nblocks]: the total), or
-// what is wrong with the first block that breaks a rule
-static std::string level_offsets(const artemis_pack_t *p, int block0, int nblocks, int ncomp, const int *shift, std::vector<long> &off) {
-  off.assign(static_cast<size_t>(nblocks) + 1, 0);
-  const int nx[3] = {p->nx1, p->nx2, p->nx3};
-  for (int b = 0; b < nblocks; ++b) {
-    const int s = shift[b];
-    if (s > artemis::FIELDS_MAX_SHIFT || s < -artemis::FIELDS_MAX_SHIFT)
-      return "pack fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", |shift| <= 3 is built";
-    long zones = 1;
-    for (int d = 0; d < 3; ++d) {
-      if (s > 0 && nx[d] > 1 && nx[d] % (1 << s) != 0)
-        return "pack fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", and its nx" +
-               std::to_string(d + 1) + " = " + std::to_string(nx[d]) + " is not divisible by " + std::to_string(1 << s);
-      zones *= artemis::level_extent(nx[d], s);
-    }
-    off[static_cast<size_t>(b) + 1] = off[static_cast<size_t>(b)] + zones * ncomp;
-  }
-  return "";
 }
 size_t artemis_hip_pack_fields_level_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                            const int *shift_host) {
-  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return 0;
-  artemis::FieldSelection S;
-  if (*field_selection(p, nsel, sel, S)) return 0;
-  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0 || (nblocks > 0 && !shift_host)) return 0;
-  std::vector<long> off;
-  if (!level_offsets(p, block0, nblocks, S.ncomp, shift_host, off).empty()) return 0;
-  return static_cast<size_t>(off.back()) * (single ? sizeof(float) : sizeof(double));
+  return fields_bytes(PACK_FIELDS_LEVEL, p, block0, nblocks, nsel, sel, single, 0, shift_host, false);
 }
 int artemis_hip_pack_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                   const int *shift_host, void *out_dev, void *stream) {
-  if (int rc = validate(p)) return rc;
-  artemis::FieldSelection F;
-  const char *bad = field_selection(p, nsel, sel, F);
-  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
-  if (nsel == 0) return fail(ARTEMIS_HIP_EINVAL, "pack fields level: no variables");
-  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
-    return fail(ARTEMIS_HIP_EINVAL, "pack fields level: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
-  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
-    return fail(ARTEMIS_HIP_EINVAL, "pack fields level: the primitive tables of the fluids asked for are required");
-  if (nblocks == 0) return 0;
-  if (!shift_host) return fail(ARTEMIS_HIP_EINVAL, "pack fields level: null shift_host");
-  std::vector<long> off;
-  const std::string rule = level_offsets(p, block0, nblocks, F.ncomp, shift_host, off);
-  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
-  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "pack fields level: null out_dev");
-  artemis::launch_pack_fields_level(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, shift_host, off.data(), out_dev, S(stream));
+  FieldsPlan P;
+  if (int rc = fields_launch(PACK_FIELDS_LEVEL, p, block0, nblocks, nsel, sel, 0, shift_host, out_dev, nullptr, P)) return rc;
+  if (P.empty) return 0;
+  artemis::launch_pack_fields_level(artemis::make_pack_view(*p), block0, nblocks, P.F, single != 0, shift_host, P.off.data(), out_dev, S(stream));
   return after_launch("pack_fields_level");
 }
-// the axes of artemis_hip_reduce_fields: "" and the zones a block leaves, or what is wrong with them
-static std::string reduce_axes(const artemis_pack_t *p, int axes, long &zones) {
-  const int nx[3] = {p->nx1, p->nx2, p->nx3};
-  zones = 1;
-  if (axes < 1 || axes > 7) return "reduce fields: axes = " + std::to_string(axes) + ", a non-empty mask of x1 (1), x2 (2), x3 (4) is taken";
-  for (int d = 0; d < 3; ++d) {
-    if (((axes >> d) & 1) && nx[d] < 2) return "reduce fields: x" + std::to_string(d + 1) + " has one zone and is not a direction to reduce";
-    if (!((axes >> d) & 1)) zones *= nx[d];
-  }
-  return "";
-}
-static bool reduce_sizes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int axes, artemis::FieldSelection &F,
-                         long &zones) {
-  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return false;
-  if (*field_selection(p, nsel, sel, F) || nsel == 0) return false;
-  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0) return false;
-  return reduce_axes(p, axes, zones).empty();
-}
 size_t artemis_hip_reduce_fields_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes) {
-  artemis::FieldSelection F;
-  long zones;
-  if (!reduce_sizes(p, block0, nblocks, nsel, sel, axes, F, zones)) return 0;
-  return static_cast<size_t>(nblocks) * (F.ncomp + 1) * zones * (single ? sizeof(float) : sizeof(double));
+  return fields_bytes(REDUCE_FIELDS, p, block0, nblocks, nsel, sel, single, axes, nullptr, false);
 }
 size_t artemis_hip_reduce_fields_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                             int axes) {
-  artemis::FieldSelection F;
-  long zones;
-  if (!reduce_sizes(p, block0, nblocks, nsel, sel, axes, F, zones)) return 0;
-  const int nx[3] = {p->nx1, p->nx2, p->nx3};
-  return static_cast<size_t>(artemis::reduce_fields_work_elements(nx, nblocks, F.ncomp, axes)) * sizeof(double);
+  return fields_bytes(REDUCE_FIELDS, p, block0, nblocks, nsel, sel, single, axes, nullptr, true);
 }
 int artemis_hip_reduce_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
                               void *out_dev, void *work_dev, void *stream) {
-  if (int rc = validate(p)) return rc;
-  artemis::FieldSelection F;
-  const char *bad = field_selection(p, nsel, sel, F);
-  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
-  if (nsel == 0) return fail(ARTEMIS_HIP_EINVAL, "reduce fields: no variables");
-  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
-    return fail(ARTEMIS_HIP_EINVAL, "reduce fields: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
-  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
-    return fail(ARTEMIS_HIP_EINVAL, "reduce fields: the primitive tables of the fluids asked for are required");
-  long zones;
-  const std::string rule = reduce_axes(p, axes, zones);
-  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
-  if (nblocks == 0) return 0;
-  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "reduce fields: null out_dev");
-  const int nx[3] = {p->nx1, p->nx2, p->nx3};
-  if (!work_dev && artemis::reduce_fields_work_elements(nx, nblocks, F.ncomp, axes) > 0)
-    return fail(ARTEMIS_HIP_EINVAL, "reduce fields: null work_dev");
-  artemis::launch_reduce_fields(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, axes, out_dev, static_cast<double *>(work_dev),
+  FieldsPlan P;
+  if (int rc = fields_launch(REDUCE_FIELDS, p, block0, nblocks, nsel, sel, axes, nullptr, out_dev, work_dev, P)) return rc;
+  if (P.empty) return 0;
+  artemis::launch_reduce_fields(artemis::make_pack_view(*p), block0, nblocks, P.F, single != 0, axes, out_dev, static_cast<double *>(work_dev),
                                 S(stream));
   return after_launch("reduce_fields");
 }
-// the shifts of artemis_hip_reduce_fields_level: "" and the element offset of every block (off[nblocks]: the total), or what
-// is wrong with the first block that breaks a rule.  Only the KEPT extents (active, outside axes) change with the shift.
-static std::string reduce_level_offsets(const artemis_pack_t *p, int block0, int nblocks, int ncomp, int axes, const int *shift,
-                                        std::vector<long> &off) {
-  off.assign(static_cast<size_t>(nblocks) + 1, 0);
-  const int nx[3] = {p->nx1, p->nx2, p->nx3};
-  for (int b = 0; b < nblocks; ++b) {
-    const int s = shift[b];
-    if (s > artemis::FIELDS_MAX_SHIFT || s < -artemis::FIELDS_MAX_SHIFT)
-      return "reduce fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", |shift| <= 3 is built";
-    long zones = 1;
-    for (int d = 0; d < 3; ++d) {
-      if (s > 0 && !((axes >> d) & 1) && nx[d] > 1 && nx[d] % (1 << s) != 0)
-        return "reduce fields level: block " + std::to_string(block0 + b) + " has shift " + std::to_string(s) + ", and its kept nx" +
-               std::to_string(d + 1) + " = " + std::to_string(nx[d]) + " is not divisible by " + std::to_string(1 << s);
-      zones *= artemis::reduce_level_extent(nx[d], s, axes, d);
-    }
-    off[static_cast<size_t>(b) + 1] = off[static_cast<size_t>(b)] + zones * (ncomp + 1);
-  }
-  return "";
-}
 size_t artemis_hip_reduce_fields_level_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
                                              const int *shift_host) {
-  artemis::FieldSelection F;
-  long zones;
-  if (!reduce_sizes(p, block0, nblocks, nsel, sel, axes, F, zones) || (nblocks > 0 && !shift_host)) return 0;
-  std::vector<long> off;
-  if (!reduce_level_offsets(p, block0, nblocks, F.ncomp, axes, shift_host, off).empty()) return 0;
-  return static_cast<size_t>(off.back()) * (single ? sizeof(float) : sizeof(double));
+  return fields_bytes(REDUCE_FIELDS_LEVEL, p, block0, nblocks, nsel, sel, single, axes, shift_host, false);
 }
 size_t artemis_hip_reduce_fields_level_work_bytes(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                                   int axes, const int *shift_host) {
-  if (artemis_hip_reduce_fields_level_bytes(p, block0, nblocks, nsel, sel, single, axes, shift_host) == 0) return 0;
-  artemis::FieldSelection F;
-  field_selection(p, nsel, sel, F);
-  const int nx[3] = {p->nx1, p->nx2, p->nx3};
-  return static_cast<size_t>(artemis::reduce_fields_level_work_elements(nx, nblocks, F.ncomp, axes)) * sizeof(double);
+  return fields_bytes(REDUCE_FIELDS_LEVEL, p, block0, nblocks, nsel, sel, single, axes, shift_host, true);
 }
 int artemis_hip_reduce_fields_level(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single, int axes,
                                     const int *shift_host, void *out_dev, void *work_dev, void *stream) {
-  if (int rc = validate(p)) return rc;
-  artemis::FieldSelection F;
-  const char *bad = field_selection(p, nsel, sel, F);
-  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
-  if (nsel == 0) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: no variables");
-  if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
-    return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: blocks [%d, %d + %d) are not inside the pack's %d", block0, block0, nblocks, p->nblocks);
-  if ((F.want_gas && !p->gas.prim) || (F.want_dust && !p->dust.prim))
-    return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: the primitive tables of the fluids asked for are required");
-  long zones;
-  std::string rule = reduce_axes(p, axes, zones);
-  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
-  if (nblocks == 0) return 0;
-  if (!shift_host) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: null shift_host");
-  std::vector<long> off;
-  rule = reduce_level_offsets(p, block0, nblocks, F.ncomp, axes, shift_host, off);
-  if (!rule.empty()) return fail(ARTEMIS_HIP_EINVAL, "%s", rule.c_str());
-  if (!out_dev) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: null out_dev");
-  if (!work_dev) return fail(ARTEMIS_HIP_EINVAL, "reduce fields level: null work_dev");
-  artemis::launch_reduce_fields_level(artemis::make_pack_view(*p), block0, nblocks, F, single != 0, axes, shift_host, off.data(), out_dev,
+  FieldsPlan P;
+  if (int rc = fields_launch(REDUCE_FIELDS_LEVEL, p, block0, nblocks, nsel, sel, axes, shift_host, out_dev, work_dev, P)) return rc;
+  if (P.empty) return 0;
+  artemis::launch_reduce_fields_level(artemis::make_pack_view(*p), block0, nblocks, P.F, single != 0, axes, shift_host, P.off.data(), out_dev,
                                       static_cast<double *>(work_dev), S(stream));
   return after_launch("reduce_fields_level");
 }

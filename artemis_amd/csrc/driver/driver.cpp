@@ -32,6 +32,7 @@
 #include "parameter_input.hpp"
 #include "block_tree.hpp"
 #include "checkpoint_hooks.hpp"
+#include "fields_host.hpp"
 #include "outputs_hooks.hpp"
 
 // The device kernel of the history integrals is referenced weakly: a host that exports the driver's C ABI without it (the
@@ -95,6 +96,14 @@ struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
+};
+
+// What artemis_sim_impl::plan_fields makes of a FieldRequest (outputs_hooks.hpp) on this rank's blocks
+struct FieldPlan {
+  int ncomp = 0, rows = 0;      // components of the variables; rows of a block: ncomp, and the volume where axes are set
+  std::vector<int> comp0;       // first component of every variable
+  std::vector<int> shift;       // per block: its level - the level asked for (0 without one)
+  std::vector<long> off;        // element offset of every block in the output, off[nb] the total
 };
 
 // A field group: [nb][nvar][N] doubles + the device table of [nb*nvar] pointers into it.
@@ -507,22 +516,14 @@ struct artemis_sim_impl {
   int history(double *out);
   DevBuf hist_sums, hist_scratch; // artemis_hip_history_sums: its result and its rows of partial sums, sized for this pack
   int history_device(double *out);
-  // artemis_sim_gather_fields: the device staging buffer of artemis_hip_pack_fields -- a whole number of blocks and at
-  // most FIELDS_STAGE_MB (default 256) MiB, one block where a block is larger; allocated by the first gather
-  DevBuf field_stage;
-  size_t gather_fields(const std::vector<int> &codes, bool single, void *host_out);
+  // artemis_sim_gather_fields*: the device staging buffer of the artemis_hip_* field kernels -- a whole number of blocks
+  // and at most FIELDS_STAGE_MB (default 256) MiB, one block where a block is larger; allocated by the first gather.
+  // field_work: the work buffer of the reducing kernels, allocated by the first gather that needs one
+  DevBuf field_stage, field_work;
+  FieldPlan plan_fields(const artemis_out::FieldRequest &req);
+  size_t gather_fields(const artemis_out::FieldRequest &req, void *host_out, long *offsets);
   void host_block_components(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, std::vector<Real> &vals,
                              std::vector<Real> *vol);
-  // ... resampled to refinement level `level` (artemis_sim_gather_fields_level); offsets: nb + 1 element offsets or null
-  size_t gather_fields_level(const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets);
-  // ... integrated over the directions of `axes` (artemis_sim_gather_fields_reduced); field_work: the device work buffer
-  // of artemis_hip_reduce_fields, allocated by the first reduced gather that needs one
-  DevBuf field_work;
-  size_t gather_fields_reduced(const std::vector<int> &codes, bool single, int axes, void *host_out);
-  // ... and brought to refinement level `level` along the kept directions (artemis_sim_gather_fields_reduced_level)
-  size_t gather_fields_reduced_level(const std::vector<int> &codes, bool single, int axes, int level, void *host_out, long *offsets);
-  // the host loop of both: block b reduced at its own resolution into cur, [ncomp + 1][n3'][n2'][n1'] doubles, W last
-  void host_reduce_block(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, int axes, std::vector<Real> &cur);
   int finest_level() const { // the finest level this run's mesh can ever hold
     int f = adaptive ? amr_max_level : 0;
     for (const Region &r : regions) f = std::max(f, r.level);
@@ -3614,363 +3615,102 @@ void artemis_sim_impl::host_block_components(int b, const std::vector<int> &code
       }
 }
 
-// Field output: the variables `codes` (enum artemis_field_var) of this rank's interior zones as [block][component][nk][nj]
-// [ni], double or float, formed from the primitives of the current buffer with PrimToCons's expressions: by
-// artemis_hip_pack_fields into a bounded staging buffer, one copy per block range (kernels_fields.hip), or -- a library
-// without that kernel -- in a host loop over the downloaded primitives.  Nothing is materialised: cons_valid stays as it is.
-size_t artemis_sim_impl::gather_fields(const std::vector<int> &codes, bool single, void *host_out) {
+// A field request on this rank's blocks (outputs_hooks.hpp, FieldRequest): the components of its variables, the rows and
+// the shift of every block, and where each block begins in the output.  Throws, in this order, for an unknown variable,
+// for no variables (a request with neither axes nor level may be empty: it gathers nothing), where the axes break
+// reduce_rule, and for the first block whose shift breaks level_rule.
+FieldPlan artemis_sim_impl::plan_fields(const artemis_out::FieldRequest &req) {
   const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
-  std::vector<int> comp0;
-  int ncomp = 0;
-  for (const int code : codes) {
+  FieldPlan P;
+  for (const int code : req.codes) {
     const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
     if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
-    comp0.push_back(ncomp), ncomp += n;
+    P.comp0.push_back(P.ncomp), P.ncomp += n;
   }
-  const size_t zones = static_cast<size_t>(mbnx[0]) * mbnx[1] * mbnx[2], esz = single ? sizeof(float) : sizeof(double);
-  const size_t block_bytes = static_cast<size_t>(ncomp) * zones * esz;
-  if (!host_out || block_bytes == 0) return static_cast<size_t>(nb) * block_bytes;
-  if (artemis_hip_pack_fields) {
-    const artemis_pack_t p = make_pack(base);
-    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
-    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
-    const int per = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(nb), cap / block_bytes)));
-    const size_t need = (static_cast<size_t>(per) * block_bytes + sizeof(double) - 1) / sizeof(double);
-    if (field_stage.n < need) field_stage.alloc(need);
-    for (int b0 = 0; b0 < nb; b0 += per) {
-      const int n = std::min(per, nb - b0);
-      CK(artemis_hip_pack_fields(&p, b0, n, static_cast<int>(codes.size()), codes.data(), single ? 1 : 0, field_stage.p, stream), "pack fields");
-      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(b0) * block_bytes, field_stage.p,
-                               static_cast<size_t>(n) * block_bytes, stream), "d2h");
-      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffer)
-    }
-    return static_cast<size_t>(nb) * block_bytes;
+  if (P.ncomp == 0 && (req.axes || req.has_level)) throw std::runtime_error("fields: no variables");
+  if (req.axes) {
+    const std::string bad = artemis_out::reduce_rule(req.axes, mbnx);
+    if (!bad.empty()) throw std::runtime_error("reduced fields: " + bad);
   }
-  std::vector<Real> q;
-  for (int b = 0; b < nb; ++b) {
-    host_block_components(b, codes, comp0, ncomp, q, nullptr);
-    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(b) * block_bytes;
-    for (size_t e = 0; e < q.size(); ++e) {
-      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(q[e]);
-      else reinterpret_cast<double *>(ob)[e] = q[e];
-    }
-  }
-  return static_cast<size_t>(nb) * block_bytes;
+  P.rows = P.ncomp + (req.axes ? 1 : 0);
+  P.shift.assign(static_cast<size_t>(nb), 0);
+  for (int b = 0; b < nb && req.has_level; ++b) P.shift[b] = blocks[b].level - req.level;
+  int b = -1;
+  if (!artemis_fields::block_offsets(mbnx, P.rows, req.axes, nb, P.shift.data(), P.off, b).empty())
+    throw std::runtime_error(std::string(req.axes ? "reduced fields" : "fields") + " at level " + std::to_string(req.level) + ": local block " +
+                             std::to_string(b) + " (gid " + std::to_string(blocks[b].gid) + ") on level " + std::to_string(blocks[b].level) + " " +
+                             artemis_out::level_rule(P.shift[b], req.axes, mbnx));
+  return P;
 }
 
-// The same gather with every block resampled to the zone size of refinement level `level` (artemis_driver.h "field output
-// at a level"; artemis_hip.h has the definition): block b has shift s = its level - level and follows block b - 1 in
-// host_out as [component][nk'][nj'][ni'].  artemis_hip_pack_fields_level into the staging buffer, the block ranges cut by
-// BYTES (blocks differ in size), or -- a library without that kernel -- the same tree in a host loop over the downloaded
-// primitives.  Every shift is checked before anything is written.  offsets (nb + 1 longs, or null): the element offset of
-// every block and the total.  host_out = NULL: sizes only.  Returns the bytes.
-size_t artemis_sim_impl::gather_fields_level(const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets) {
-  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
-  std::vector<int> comp0;
-  int ncomp = 0;
-  for (const int code : codes) {
-    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
-    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
-    comp0.push_back(ncomp), ncomp += n;
-  }
-  if (ncomp == 0) throw std::runtime_error("fields: no variables");
-  const size_t esz = single ? sizeof(float) : sizeof(double);
-  std::vector<int> shift(static_cast<size_t>(nb));
-  std::vector<long> off(static_cast<size_t>(nb) + 1, 0);
-  for (int b = 0; b < nb; ++b) {
-    const int s = blocks[b].level - level;
-    const std::string bad = artemis_out::level_rule(s, mbnx);
-    if (!bad.empty())
-      throw std::runtime_error("fields at level " + std::to_string(level) + ": local block " + std::to_string(b) + " (gid " + std::to_string(blocks[b].gid) +
-                               ") on level " + std::to_string(blocks[b].level) + " " + bad);
-    shift[b] = s;
-    long zones = 1;
-    for (int d = 0; d < 3; ++d) zones *= artemis_out::level_extent(mbnx[d], s);
-    off[b + 1] = off[b] + zones * ncomp;
-  }
+// Field output: the variables of `req` of this rank's interior zones, the blocks one after the other, block b as
+// [rows][nk'][nj'][ni'], double or float, formed from the primitives of the current buffer with PrimToCons's expressions
+// (artemis_driver.h "field output"; artemis_hip.h has the definition of every mode).  By the artemis_hip_* entry point of
+// the mode into a bounded staging buffer, one copy per block range -- a range takes blocks while its bytes of output and
+// of work both stay within the cap, and at least one -- or, in a library without that entry point, by the same operations
+// in the same order in a host loop over the downloaded primitives (fields_host.hpp).  Everything is checked before
+// anything is written; nothing is materialised and nothing of the run moves.  offsets (nb + 1 longs, or null): the element
+// offset of every block and the total.  host_out = NULL: sizes only.  Returns the bytes.
+size_t artemis_sim_impl::gather_fields(const artemis_out::FieldRequest &req, void *host_out, long *offsets) {
+  namespace fh = artemis_fields_host;
+  const FieldPlan P = plan_fields(req);
+  const std::vector<long> &off = P.off;
   if (offsets) std::copy(off.begin(), off.end(), offsets);
-  const size_t total = static_cast<size_t>(off[nb]) * esz;
+  const size_t esz = req.single ? sizeof(float) : sizeof(double), total = static_cast<size_t>(off[nb]) * esz;
   if (!host_out || total == 0) return total;
-  if (artemis_hip_pack_fields_level) {
+  const int nsel = static_cast<int>(req.codes.size()), single = req.single ? 1 : 0, axes = req.axes;
+  const int *sel = req.codes.data();
+  const bool device = axes ? (req.has_level ? artemis_hip_reduce_fields_level && artemis_hip_reduce_fields_level_work_bytes
+                                            : artemis_hip_reduce_fields && artemis_hip_reduce_fields_work_bytes)
+                           : (req.has_level ? artemis_hip_pack_fields_level != nullptr : artemis_hip_pack_fields != nullptr);
+  if (device) {
     const artemis_pack_t p = make_pack(base);
     const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
     const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
+    const int zero = 0; // (the work of a range is linear in its blocks, whatever their shifts)
+    const size_t work1 = !axes ? 0 : (req.has_level ? artemis_hip_reduce_fields_level_work_bytes(&p, 0, 1, nsel, sel, single, axes, &zero)
+                                                    : artemis_hip_reduce_fields_work_bytes(&p, 0, 1, nsel, sel, single, axes));
     for (int b0 = 0; b0 < nb;) {
-      int n = 1; // as many blocks as the cap holds, one where a block is larger
-      while (b0 + n < nb && static_cast<size_t>(off[b0 + n + 1] - off[b0]) * esz <= cap) ++n;
-      const size_t bytes = static_cast<size_t>(off[b0 + n] - off[b0]) * esz;
-      const size_t need = (bytes + sizeof(double) - 1) / sizeof(double);
-      if (field_stage.n < need) field_stage.alloc(need);
-      CK(artemis_hip_pack_fields_level(&p, b0, n, static_cast<int>(codes.size()), codes.data(), single ? 1 : 0, shift.data() + b0, field_stage.p, stream),
-         "pack fields level");
-      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(off[b0]) * esz, field_stage.p, bytes, stream), "d2h");
-      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffer)
-      b0 += n;
-    }
-    return total;
-  }
-  std::vector<Real> q, vol, cur, nxt;
-  for (int b = 0; b < nb; ++b) {
-    const int s = shift[b];
-    host_block_components(b, codes, comp0, ncomp, q, &vol);
-    int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
-    const size_t zin = vol.size();
-    std::vector<Real> res; // [ncomp][nk'][nj'][ni']
-    if (s > 0) {
-      // rows 0 .. ncomp - 1: N = V q, row ncomp: V; each goes s times up the tree of restriction.hpp:107-112
-      cur.assign((static_cast<size_t>(ncomp) + 1) * zin, 0.0);
-      for (int c = 0; c < ncomp; ++c)
-        for (size_t z = 0; z < zin; ++z) cur[c * zin + z] = vol[z] * q[c * zin + z];
-      std::copy(vol.begin(), vol.end(), cur.begin() + static_cast<size_t>(ncomp) * zin);
-      for (int m = 0; m < s; ++m) {
-        const bool a[3] = {n[0] > 1, n[1] > 1, n[2] > 1};
-        const int o[3] = {a[0] ? n[0] / 2 : 1, a[1] ? n[1] / 2 : 1, a[2] ? n[2] / 2 : 1};
-        const size_t zi = static_cast<size_t>(n[0]) * n[1] * n[2], zo = static_cast<size_t>(o[0]) * o[1] * o[2];
-        nxt.assign((static_cast<size_t>(ncomp) + 1) * zo, 0.0);
-        for (int c = 0; c <= ncomp; ++c) {
-          const Real *x = cur.data() + c * zi;
-          auto child = [&](int K, int J, int I, int ok, int oj, int oi) -> Real { // 0.0: the offset-1 child of an inactive direction
-            if ((ok && !a[2]) || (oj && !a[1]) || (oi && !a[0])) return 0.0;
-            const int k = a[2] ? 2 * K + ok : K, j = a[1] ? 2 * J + oj : J, i = a[0] ? 2 * I + oi : I;
-            return x[(static_cast<size_t>(k) * n[1] + j) * n[0] + i];
-          };
-          for (int K = 0; K < o[2]; ++K)
-            for (int J = 0; J < o[1]; ++J)
-              for (int I = 0; I < o[0]; ++I)
-                nxt[c * zo + (static_cast<size_t>(K) * o[1] + J) * o[0] + I] =
-                    ((child(K, J, I, 0, 0, 0) + child(K, J, I, 0, 1, 0)) + (child(K, J, I, 0, 0, 1) + child(K, J, I, 0, 1, 1))) +
-                    ((child(K, J, I, 1, 0, 0) + child(K, J, I, 1, 1, 0)) + (child(K, J, I, 1, 0, 1) + child(K, J, I, 1, 1, 1)));
-        }
-        cur.swap(nxt);
-        for (int d = 0; d < 3; ++d) n[d] = o[d];
-      }
-      const size_t zo = static_cast<size_t>(n[0]) * n[1] * n[2];
-      res.resize(static_cast<size_t>(ncomp) * zo);
-      for (int c = 0; c < ncomp; ++c)
-        for (size_t z = 0; z < zo; ++z) res[c * zo + z] = cur[c * zo + z] / cur[static_cast<size_t>(ncomp) * zo + z];
-    } else {
-      const int r = -s;
-      const int rs[3] = {n[0] > 1 ? r : 0, n[1] > 1 ? r : 0, n[2] > 1 ? r : 0};
-      const int o[3] = {n[0] << rs[0], n[1] << rs[1], n[2] << rs[2]};
-      const size_t zo = static_cast<size_t>(o[0]) * o[1] * o[2];
-      res.resize(static_cast<size_t>(ncomp) * zo);
-      for (int c = 0; c < ncomp; ++c)
-        for (int k = 0; k < o[2]; ++k)
-          for (int j = 0; j < o[1]; ++j)
-            for (int i = 0; i < o[0]; ++i)
-              res[c * zo + (static_cast<size_t>(k) * o[1] + j) * o[0] + i] =
-                  q[c * zin + (static_cast<size_t>(k >> rs[2]) * n[1] + (j >> rs[1])) * n[0] + (i >> rs[0])];
-    }
-    if (static_cast<long>(res.size()) != off[b + 1] - off[b]) throw std::runtime_error("fields at a level: size mismatch");
-    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(off[b]) * esz;
-    for (size_t e = 0; e < res.size(); ++e) {
-      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(res[e]);
-      else reinterpret_cast<double *>(ob)[e] = res[e];
-    }
-  }
-  return total;
-}
-
-void artemis_sim_impl::host_reduce_block(int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, int axes,
-                                         std::vector<Real> &cur) {
-  std::vector<Real> q, vol, nxt;
-  host_block_components(b, codes, comp0, ncomp, q, &vol);
-  int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
-  const size_t zin = vol.size();
-  cur.assign((static_cast<size_t>(ncomp) + 1) * zin, 0.0); // rows 0 .. ncomp - 1: N = V q, row ncomp: W = V
-  for (int c = 0; c < ncomp; ++c)
-    for (size_t z = 0; z < zin; ++z) cur[c * zin + z] = vol[z] * q[c * zin + z];
-  std::copy(vol.begin(), vol.end(), cur.begin() + static_cast<size_t>(ncomp) * zin);
-  for (int d = 0; d < 3; ++d) {
-    if (!((axes >> d) & 1)) continue;
-    // cur is [rows][len][inner]: x1 rows = (ncomp + 1) nz ny, inner = 1; x2 inner = nx'; x3 inner = ny' nx'
-    const size_t len = static_cast<size_t>(n[d]), inner = d == 0 ? 1 : (d == 1 ? n[0] : static_cast<size_t>(n[0]) * n[1]);
-    const size_t rows = cur.size() / (len * inner);
-    nxt.assign(rows * inner, 0.0);
-    for (size_t r = 0; r < rows; ++r)
-      for (size_t x = 0; x < inner; ++x) {
-        const Real *in = cur.data() + r * len * inner + x;
-        Real acc = 0.0;
-        if (d == 0) { // the butterfly in chunks of 64, the chunks in increasing order
-          for (size_t c0 = 0; c0 < len; c0 += 64) {
-            Real w[64], y[64];
-            for (size_t l = 0; l < 64; ++l) w[l] = (c0 + l < len) ? in[c0 + l] : 0.0;
-            for (int m = 0; m < 6; ++m) {
-              for (int l = 0; l < 64; ++l) y[l] = w[l] + w[l ^ (1 << m)];
-              std::copy(y, y + 64, w);
-            }
-            acc = (c0 == 0) ? w[0] : acc + w[0];
-          }
-        } else { // sequential, from the first element
-          acc = in[0];
-          for (size_t t = 1; t < len; ++t) acc = acc + in[t * inner];
-        }
-        nxt[r * inner + x] = acc;
-      }
-    cur.swap(nxt);
-    n[d] = 1;
-  }
-}
-
-// The same gather with every block integrated over the directions of `axes` (bit 0 x1, bit 1 x2, bit 2 x3; artemis_hip.h,
-// artemis_hip_reduce_fields, has the definition): block b is [ncomp + 1][nk'][nj'][ni'] in host_out, the reduced extents 1
-// and the volume W last.  artemis_hip_reduce_fields into the staging buffer, the block ranges cut by bytes of output AND of
-// work, or -- a library without that kernel -- the same sums in a host loop over the downloaded primitives.  Primitives
-// are read and nothing of the run moves.  host_out = NULL: the size only.  Returns the bytes.
-size_t artemis_sim_impl::gather_fields_reduced(const std::vector<int> &codes, bool single, int axes, void *host_out) {
-  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
-  std::vector<int> comp0;
-  int ncomp = 0;
-  for (const int code : codes) {
-    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
-    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
-    comp0.push_back(ncomp), ncomp += n;
-  }
-  if (ncomp == 0) throw std::runtime_error("fields: no variables");
-  const std::string bad = artemis_out::reduce_rule(axes, mbnx);
-  if (!bad.empty()) throw std::runtime_error("reduced fields: " + bad);
-  int o[3];
-  for (int d = 0; d < 3; ++d) o[d] = ((axes >> d) & 1) ? 1 : mbnx[d];
-  const size_t esz = single ? sizeof(float) : sizeof(double);
-  const size_t block_el = static_cast<size_t>(ncomp + 1) * o[0] * o[1] * o[2], block_bytes = block_el * esz;
-  const size_t total = static_cast<size_t>(nb) * block_bytes;
-  if (!host_out || total == 0) return total;
-  if (artemis_hip_reduce_fields && artemis_hip_reduce_fields_work_bytes) {
-    const artemis_pack_t p = make_pack(base);
-    const int nsel = static_cast<int>(codes.size());
-    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
-    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
-    const size_t work1 = artemis_hip_reduce_fields_work_bytes(&p, 0, 1, nsel, codes.data(), single ? 1 : 0, axes); // (linear in the blocks)
-    const size_t per = std::max(std::max(block_bytes, work1), static_cast<size_t>(1));
-    const int chunk = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(nb), cap / per)));
-    for (int b0 = 0; b0 < nb; b0 += chunk) {
-      const int n = std::min(chunk, nb - b0);
-      const size_t need = (static_cast<size_t>(n) * block_bytes + sizeof(double) - 1) / sizeof(double);
-      const size_t wneed = static_cast<size_t>(n) * work1 / sizeof(double);
-      if (field_stage.n < need) field_stage.alloc(need);
-      if (wneed > 0 && field_work.n < wneed) field_work.alloc(wneed);
-      CK(artemis_hip_reduce_fields(&p, b0, n, nsel, codes.data(), single ? 1 : 0, axes, field_stage.p, field_work.p, stream), "reduce fields");
-      CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(b0) * block_bytes, field_stage.p,
-                               static_cast<size_t>(n) * block_bytes, stream), "d2h");
-      CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffers)
-    }
-    return total;
-  }
-  std::vector<Real> cur;
-  for (int b = 0; b < nb; ++b) {
-    host_reduce_block(b, codes, comp0, ncomp, axes, cur);
-    if (cur.size() != block_el) throw std::runtime_error("reduced fields: size mismatch");
-    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(b) * block_bytes;
-    for (size_t e = 0; e < cur.size(); ++e) {
-      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(cur[e]);
-      else reinterpret_cast<double *>(ob)[e] = cur[e];
-    }
-  }
-  return total;
-}
-
-// The reduced gather on a chosen level (artemis_hip.h, artemis_hip_reduce_fields_level, has the definition): block b is
-// reduced at its own resolution, then brought to shift s = its level - level along the kept directions -- s >= 1 the pair
-// tree x[0::2] + x[1::2] per kept direction, s <= -1 an even share 2^(-|s| m) replicated -- and follows block b - 1 in host_out
-// as [ncomp + 1][nk'][nj'][ni'], W last.  Every shift is checked before anything is written.  The block ranges are cut by
-// bytes of output AND of work; a library without the kernel runs the same operations in the same order in a host loop.
-// offsets (nb + 1 longs, or null): the element offset of every block and the total.  host_out = NULL: sizes only.
-size_t artemis_sim_impl::gather_fields_reduced_level(const std::vector<int> &codes, bool single, int axes, int level, void *host_out,
-                                                     long *offsets) {
-  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
-  std::vector<int> comp0;
-  int ncomp = 0;
-  for (const int code : codes) {
-    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
-    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
-    comp0.push_back(ncomp), ncomp += n;
-  }
-  if (ncomp == 0) throw std::runtime_error("fields: no variables");
-  const std::string bad_axes = artemis_out::reduce_rule(axes, mbnx);
-  if (!bad_axes.empty()) throw std::runtime_error("reduced fields: " + bad_axes);
-  const size_t esz = single ? sizeof(float) : sizeof(double);
-  std::vector<int> shift(static_cast<size_t>(nb));
-  std::vector<long> off(static_cast<size_t>(nb) + 1, 0);
-  for (int b = 0; b < nb; ++b) {
-    const int s = blocks[b].level - level;
-    const std::string bad = artemis_out::reduce_level_rule(s, axes, mbnx);
-    if (!bad.empty())
-      throw std::runtime_error("reduced fields at level " + std::to_string(level) + ": local block " + std::to_string(b) + " (gid " +
-                               std::to_string(blocks[b].gid) + ") on level " + std::to_string(blocks[b].level) + " " + bad);
-    shift[b] = s;
-    long zones = 1;
-    for (int d = 0; d < 3; ++d) zones *= artemis_out::reduce_level_extent(mbnx[d], s, axes, d);
-    off[b + 1] = off[b] + zones * (ncomp + 1);
-  }
-  if (offsets) std::copy(off.begin(), off.end(), offsets);
-  const size_t total = static_cast<size_t>(off[nb]) * esz;
-  if (!host_out || total == 0) return total;
-  bool kept[3];
-  int m = 0, own[3]; // own: the extents the reduction at the block's own resolution leaves
-  for (int d = 0; d < 3; ++d) kept[d] = !((axes >> d) & 1) && mbnx[d] > 1, m += kept[d] ? 1 : 0, own[d] = ((axes >> d) & 1) ? 1 : mbnx[d];
-  if (artemis_hip_reduce_fields_level && artemis_hip_reduce_fields_level_work_bytes) {
-    const artemis_pack_t p = make_pack(base);
-    const int nsel = static_cast<int>(codes.size());
-    const long mb = artemis::opt(artemis::OPT_FIELDS_STAGE_MB);
-    const size_t cap = static_cast<size_t>(mb > 0 ? mb : 256) << 20;
-    const int zero = 0;
-    const size_t work1 = artemis_hip_reduce_fields_level_work_bytes(&p, 0, 1, nsel, codes.data(), single ? 1 : 0, axes, &zero); // (linear in the blocks, whatever their shifts)
-    for (int b0 = 0; b0 < nb;) {
-      int n = 1; // as many blocks as the cap holds in output and in work, one where a block is larger
+      // (of blocks of one size that takes cap / max(bytes of a block, work1), since min(cap / a, cap / b) = cap / max(a, b))
+      int n = 1;
       while (b0 + n < nb && static_cast<size_t>(off[b0 + n + 1] - off[b0]) * esz <= cap && static_cast<size_t>(n + 1) * work1 <= cap) ++n;
       const size_t bytes = static_cast<size_t>(off[b0 + n] - off[b0]) * esz;
       const size_t need = (bytes + sizeof(double) - 1) / sizeof(double), wneed = static_cast<size_t>(n) * work1 / sizeof(double);
       if (field_stage.n < need) field_stage.alloc(need);
       if (field_work.n < wneed) field_work.alloc(wneed);
-      CK(artemis_hip_reduce_fields_level(&p, b0, n, nsel, codes.data(), single ? 1 : 0, axes, shift.data() + b0, field_stage.p, field_work.p, stream),
-         "reduce fields level");
+      const int *shift = P.shift.data() + b0;
+      if (axes && req.has_level)
+        CK(artemis_hip_reduce_fields_level(&p, b0, n, nsel, sel, single, axes, shift, field_stage.p, field_work.p, stream), "reduce fields level");
+      else if (axes) CK(artemis_hip_reduce_fields(&p, b0, n, nsel, sel, single, axes, field_stage.p, field_work.p, stream), "reduce fields");
+      else if (req.has_level) CK(artemis_hip_pack_fields_level(&p, b0, n, nsel, sel, single, shift, field_stage.p, stream), "pack fields level");
+      else CK(artemis_hip_pack_fields(&p, b0, n, nsel, sel, single, field_stage.p, stream), "pack fields");
       CK(artemis_rt_memcpy_d2h(static_cast<char *>(host_out) + static_cast<size_t>(off[b0]) * esz, field_stage.p, bytes, stream), "d2h");
       CK(artemis_rt_stream_sync(stream), "sync"); // (the next range reuses the buffers)
       b0 += n;
     }
     return total;
   }
-  std::vector<Real> cur, nxt;
+  bool kept[3]; // the directions a shift acts along: active and outside axes
+  for (int d = 0; d < 3; ++d) kept[d] = !((axes >> d) & 1) && mbnx[d] > 1;
+  std::vector<Real> q, vol, cur;
   for (int b = 0; b < nb; ++b) {
-    const int s = shift[b], r = s < 0 ? -s : s;
-    host_reduce_block(b, codes, comp0, ncomp, axes, cur);
-    int n[3] = {own[0], own[1], own[2]};
-    if (s > 0) {
-      for (int d = 0; d < 3; ++d) { // x = x[0::2] + x[1::2] along each kept direction, s times
-        if (!kept[d]) continue;
-        for (int t = 0; t < s; ++t) {
-          const size_t inner = d == 0 ? 1 : (d == 1 ? n[0] : static_cast<size_t>(n[0]) * n[1]), half = static_cast<size_t>(n[d]) / 2;
-          const size_t rows = cur.size() / (static_cast<size_t>(n[d]) * inner);
-          nxt.assign(rows * half * inner, 0.0);
-          for (size_t row = 0; row < rows; ++row)
-            for (size_t h = 0; h < half; ++h)
-              for (size_t x = 0; x < inner; ++x)
-                nxt[(row * half + h) * inner + x] = cur[(row * 2 * half + 2 * h) * inner + x] + cur[(row * 2 * half + 2 * h + 1) * inner + x];
-          cur.swap(nxt);
-          n[d] = static_cast<int>(half);
-        }
-      }
-    } else if (s < 0) {
-      const Real share = std::ldexp(1.0, -r * m); // 2^(-|s| m): an exact scaling
-      const int rs[3] = {kept[0] ? r : 0, kept[1] ? r : 0, kept[2] ? r : 0};
-      const int o[3] = {n[0] << rs[0], n[1] << rs[1], n[2] << rs[2]};
-      const size_t zi = static_cast<size_t>(n[0]) * n[1] * n[2], zo = static_cast<size_t>(o[0]) * o[1] * o[2];
-      nxt.assign((static_cast<size_t>(ncomp) + 1) * zo, 0.0);
-      for (int c = 0; c <= ncomp; ++c)
-        for (int k = 0; k < o[2]; ++k)
-          for (int j = 0; j < o[1]; ++j)
-            for (int i = 0; i < o[0]; ++i) {
-              const Real x = cur[c * zi + (static_cast<size_t>(k >> rs[2]) * n[1] + (j >> rs[1])) * n[0] + (i >> rs[0])];
-              nxt[c * zo + (static_cast<size_t>(k) * o[1] + j) * o[0] + i] = m > 0 ? x * share : x;
-            }
-      cur.swap(nxt);
+    const int s = P.shift[b];
+    int n[3] = {mbnx[0], mbnx[1], mbnx[2]};
+    host_block_components(b, req.codes, P.comp0, P.ncomp, q, (axes || s > 0) ? &vol : nullptr);
+    if (axes) { // integrals: reduced at the block's own resolution, then pair sums down or an even share up
+      fh::weigh(q, vol, P.ncomp, cur);
+      fh::reduce_axes(cur, n, axes);
+      if (s > 0) fh::pair_sums(cur, n, s, kept);
+      else if (s < 0) fh::share(cur, P.rows, n, -s, kept);
+    } else if (s > 0) { // means: the restriction tree down, replication up
+      fh::weigh(q, vol, P.ncomp, cur);
+      fh::restrict_means(cur, P.ncomp, n, s);
+    } else {
+      cur.swap(q);
+      if (s < 0) fh::replicate(cur, P.rows, n, -s, kept, 1.0, false);
     }
-    if (static_cast<long>(cur.size()) != off[b + 1] - off[b]) throw std::runtime_error("reduced fields at a level: size mismatch");
-    char *ob = static_cast<char *>(host_out) + static_cast<size_t>(off[b]) * esz;
-    for (size_t e = 0; e < cur.size(); ++e) {
-      if (single) reinterpret_cast<float *>(ob)[e] = static_cast<float>(cur[e]);
-      else reinterpret_cast<double *>(ob)[e] = cur[e];
-    }
+    if (static_cast<long>(cur.size()) != off[b + 1] - off[b]) throw std::runtime_error("fields: size mismatch");
+    fh::store(cur, req.single, static_cast<char *>(host_out) + static_cast<size_t>(off[b]) * esz);
   }
   return total;
 }
@@ -4528,21 +4268,11 @@ const std::vector<std::string> &overrides_of(const artemis_sim_t *sim) { return 
 State *&state_of(artemis_sim_t *sim) { return sim->outputs; }
 const State *state_of(const artemis_sim_t *sim) { return sim->outputs; }
 int history_sums(artemis_sim_t *sim, double *out) { return sim->p->history_device(out); }
-size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out) {
-  return sim->p->gather_fields(codes, single, host_out);
+size_t gather_fields(artemis_sim_t *sim, const FieldRequest &req, void *host_out, long *offsets) {
+  return sim->p->gather_fields(req, host_out, offsets);
 }
 size_t scatter_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, const void *host_in, double time) {
   return sim->p->scatter_fields(codes, single, host_in, time);
-}
-size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets) {
-  return sim->p->gather_fields_level(codes, single, level, host_out, offsets);
-}
-size_t gather_fields_reduced(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, void *host_out) {
-  return sim->p->gather_fields_reduced(codes, single, axes, host_out);
-}
-size_t gather_fields_reduced_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, int level, void *host_out,
-                                   long *offsets) {
-  return sim->p->gather_fields_reduced_level(codes, single, axes, level, host_out, offsets);
 }
 FieldsLayout fields_layout(artemis_sim_t *sim) {
   const artemis_sim_impl &S = *sim->p;
@@ -4826,7 +4556,10 @@ int artemis_sim_history_device(artemis_sim_t *s, double *out) {
   GUARD(n = s->p->history_device(out), return -1)
   return n;
 }
-long artemis_sim_gather_fields(artemis_sim_t *s, int nvar, const char *const *names, int single, void *host_out) {
+// The artemis_sim_gather_fields* entry points: the names become the codes of `req` (`who` names the entry point to an
+// unknown one), then the gather.  Returns the components with host_out, the bytes without, -1 on failure.
+static long gather_entry(artemis_sim_t *s, const char *who, int nvar, const char *const *names, artemis_out::FieldRequest req,
+                         void *host_out, long *block_offsets) {
   long ret = -1;
   if (!s->dead.empty()) {
     g_sim_err = s->dead;
@@ -4834,95 +4567,34 @@ long artemis_sim_gather_fields(artemis_sim_t *s, int nvar, const char *const *na
   }
   auto gather = [&]() {
     const artemis_out::Clock c = artemis_out::clock_of(s);
-    std::vector<int> codes;
     int ncomp = 0;
     for (int v = 0; v < nvar; ++v) {
       const std::string name = (names && names[v]) ? names[v] : "";
       const int code = artemis_out::field_var_code(name);
       const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
-      if (n == 0) throw std::runtime_error("gather_fields: unknown variable " + name);
-      codes.push_back(code);
+      if (n == 0) throw std::runtime_error(std::string(who) + ": unknown variable " + name);
+      req.codes.push_back(code);
       ncomp += n;
     }
-    const size_t bytes = s->p->gather_fields(codes, single != 0, host_out);
+    const size_t bytes = s->p->gather_fields(req, host_out, block_offsets);
     ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
   };
   GUARD(gather(), return -1)
   return ret;
+}
+long artemis_sim_gather_fields(artemis_sim_t *s, int nvar, const char *const *names, int single, void *host_out) {
+  return gather_entry(s, "gather_fields", nvar, names, {{}, single != 0, 0, false, 0}, host_out, nullptr);
 }
 long artemis_sim_gather_fields_level(artemis_sim_t *s, int nvar, const char *const *names, int single, int level, void *host_out,
                                      long *block_offsets) {
-  long ret = -1;
-  if (!s->dead.empty()) {
-    g_sim_err = s->dead;
-    return -1;
-  }
-  auto gather = [&]() {
-    const artemis_out::Clock c = artemis_out::clock_of(s);
-    std::vector<int> codes;
-    int ncomp = 0;
-    for (int v = 0; v < nvar; ++v) {
-      const std::string name = (names && names[v]) ? names[v] : "";
-      const int code = artemis_out::field_var_code(name);
-      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
-      if (n == 0) throw std::runtime_error("gather_fields_level: unknown variable " + name);
-      codes.push_back(code);
-      ncomp += n;
-    }
-    const size_t bytes = s->p->gather_fields_level(codes, single != 0, level, host_out, block_offsets);
-    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
-  };
-  GUARD(gather(), return -1)
-  return ret;
+  return gather_entry(s, "gather_fields_level", nvar, names, {{}, single != 0, 0, true, level}, host_out, block_offsets);
 }
 long artemis_sim_gather_fields_reduced(artemis_sim_t *s, int nvar, const char *const *names, int single, int axes, void *host_out) {
-  long ret = -1;
-  if (!s->dead.empty()) {
-    g_sim_err = s->dead;
-    return -1;
-  }
-  auto gather = [&]() {
-    const artemis_out::Clock c = artemis_out::clock_of(s);
-    std::vector<int> codes;
-    int ncomp = 0;
-    for (int v = 0; v < nvar; ++v) {
-      const std::string name = (names && names[v]) ? names[v] : "";
-      const int code = artemis_out::field_var_code(name);
-      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
-      if (n == 0) throw std::runtime_error("gather_fields_reduced: unknown variable " + name);
-      codes.push_back(code);
-      ncomp += n;
-    }
-    const size_t bytes = s->p->gather_fields_reduced(codes, single != 0, axes, host_out);
-    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
-  };
-  GUARD(gather(), return -1)
-  return ret;
+  return gather_entry(s, "gather_fields_reduced", nvar, names, {{}, single != 0, artemis_out::reducing_axes(axes), false, 0}, host_out, nullptr);
 }
 long artemis_sim_gather_fields_reduced_level(artemis_sim_t *s, int nvar, const char *const *names, int single, int axes, int level,
                                              void *host_out, long *block_offsets) {
-  long ret = -1;
-  if (!s->dead.empty()) {
-    g_sim_err = s->dead;
-    return -1;
-  }
-  auto gather = [&]() {
-    const artemis_out::Clock c = artemis_out::clock_of(s);
-    std::vector<int> codes;
-    int ncomp = 0;
-    for (int v = 0; v < nvar; ++v) {
-      const std::string name = (names && names[v]) ? names[v] : "";
-      const int code = artemis_out::field_var_code(name);
-      const int n = code < 0 ? 0 : artemis_out::field_var_components(code, c.ns_gas, c.ns_dust);
-      if (n == 0) throw std::runtime_error("gather_fields_reduced_level: unknown variable " + name);
-      codes.push_back(code);
-      ncomp += n;
-    }
-    const size_t bytes = s->p->gather_fields_reduced_level(codes, single != 0, axes, level, host_out, block_offsets);
-    ret = host_out ? static_cast<long>(ncomp) : static_cast<long>(bytes);
-  };
-  GUARD(gather(), return -1)
-  return ret;
+  return gather_entry(s, "gather_fields_reduced_level", nvar, names, {{}, single != 0, artemis_out::reducing_axes(axes), true, level}, host_out, block_offsets);
 }
 int artemis_sim_errors(artemis_sim_t *s, double *out) {
   int n = -1;

@@ -123,7 +123,7 @@ void parse_fld(artemis_host::ParameterInput &pin, const Clock &c, OutBlock &b) {
     b.has_level = true, b.level = pin.GetInteger(b.name, "level");
     // the worst shifts this deck can ever produce: its finest possible level and the root grid
     for (const int lv : {c.finest_level, 0}) {
-      const std::string rule = level_rule(lv - b.level, c.mbnx);
+      const std::string rule = level_rule(lv - b.level, 0, c.mbnx);
       if (b.skip.empty() && !rule.empty()) b.skip = "level " + std::to_string(b.level) + ": a block on level " + std::to_string(lv) + " " + rule;
     }
   }
@@ -141,7 +141,7 @@ void parse_fld(artemis_host::ParameterInput &pin, const Clock &c, OutBlock &b) {
     // the worst shifts this deck can ever produce: its finest possible level and the root grid
     for (const int lv : {c.finest_level, 0}) {
       if (!rule.empty() || !b.skip.empty()) break;
-      const std::string bad = reduce_level_rule(lv - b.reduce_level, b.reduce, c.mbnx);
+      const std::string bad = level_rule(lv - b.reduce_level, b.reduce, c.mbnx);
       if (!bad.empty()) rule = "reduce_level " + std::to_string(b.reduce_level) + ": a block on level " + std::to_string(lv) + " " + bad;
     }
     if (b.skip.empty() && !rule.empty()) b.skip = rule;
@@ -265,26 +265,36 @@ void write_file(const std::string &name, const void *data, size_t bytes) {
   if (std::fclose(f) != 0 || bad) throw std::runtime_error("writing " + name + " failed");
 }
 
-// reduce != 0: version 3 -- "reduce": the names of the directions summed over; the variables end with "volume" (W); every
-// block entry carries its reduced nx and its element offset.
-// reduce == 0 and level = null: version 1.
-// reduce == 0 and a level: version 2 -- "level", and every block entry carries the nx it was written with and the element
-// offset of its first value in its rank's part (the blocks of a rank follow each other in index order).
-// reduce != 0 and a reduce_level: version 4 -- version 3 with "reduce_level", every block entry carrying the nx it was
-// brought to along the kept directions and, as in version 2, its element offset in its rank's part.
-std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<int> &codes, bool single, const int *level, int reduce,
-                      const int *reduce_level = nullptr) {
-  std::string red;
-  for (int d = 0; d < 3; ++d)
-    if ((reduce >> d) & 1) red += std::string(red.empty() ? "" : ", ") + "\"x" + std::to_string(d + 1) + "\"";
-  std::string j = std::string("{\"format\": \"artemis_fld\", \"version\": ") + (reduce && reduce_level ? "4, \"reduce\": [" + red + "], \"reduce_level\": " + std::to_string(*reduce_level) : reduce ? "3, \"reduce\": [" + red + "]" : level ? "2, \"level\": " + std::to_string(*level) : std::string("1")) +
-                  ", \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
-                  ", \"cycle\": " + std::to_string(c.ncycle) + ", \"coordinates\": " + json_str(L.coordinates) +
-                  ", \"ndim\": " + std::to_string(L.ndim) + ", \"nghost\": 0, \"dtype\": " + (single ? "\"<f4\"" : "\"<f8\"") +
-                  ", \"gamma\": " + json_num(L.gamma) + ", \"ns_gas\": " + std::to_string(c.ns_gas) + ", \"ns_dust\": " + std::to_string(c.ns_dust) +
-                  ", \"nranks\": " + std::to_string(L.nranks);
-  const std::string nx = "[" + std::to_string(L.nx[0]) + ", " + std::to_string(L.nx[1]) + ", " + std::to_string(L.nx[2]) + "]";
-  j += ", \"nx\": " + nx + ",\n \"variables\": [";
+// The request of a `fld` block: the one place its parsed keys become one
+FieldRequest request_of(const OutBlock &b) {
+  FieldRequest req;
+  req.codes = b.codes, req.single = b.single, req.axes = b.reduce;
+  req.has_level = b.reduce ? b.has_reduce_level : b.has_level, req.level = b.reduce ? b.reduce_level : b.level;
+  return req;
+}
+
+// The version says which of the two choices a dump made: 1 neither, 2 a level ("level"), 3 axes ("reduce": the names of
+// the directions summed over), 4 both ("reduce" and "reduce_level").  With axes the variables end with "volume" (W).
+// From version 2 on every block entry carries the nx it was written with and the element offset of its first value in its
+// rank's part (the blocks of a rank follow each other in index order).
+std::string meta_json(const Clock &c, const FieldsLayout &L, const FieldRequest &req) {
+  const std::vector<int> &codes = req.codes;
+  const int version = req.axes ? (req.has_level ? 4 : 3) : (req.has_level ? 2 : 1);
+  std::string j = "{\"format\": \"artemis_fld\", \"version\": " + std::to_string(version);
+  if (req.axes) {
+    j += ", \"reduce\": [";
+    for (int d = 0, n = 0; d < 3; ++d)
+      if ((req.axes >> d) & 1) j += std::string(n++ ? ", " : "") + "\"x" + std::to_string(d + 1) + "\"";
+    j += "]";
+  }
+  if (req.has_level) j += std::string(req.axes ? ", \"reduce_level\": " : ", \"level\": ") + std::to_string(req.level);
+  j += ", \"time\": " + json_num(c.time) + ", \"dt\": " + json_num(c.dt) +
+       ", \"cycle\": " + std::to_string(c.ncycle) + ", \"coordinates\": " + json_str(L.coordinates) +
+       ", \"ndim\": " + std::to_string(L.ndim) + ", \"nghost\": 0, \"dtype\": " + (req.single ? "\"<f4\"" : "\"<f8\"") +
+       ", \"gamma\": " + json_num(L.gamma) + ", \"ns_gas\": " + std::to_string(c.ns_gas) + ", \"ns_dust\": " + std::to_string(c.ns_dust) +
+       ", \"nranks\": " + std::to_string(L.nranks);
+  j += ", \"nx\": [" + std::to_string(L.nx[0]) + ", " + std::to_string(L.nx[1]) + ", " + std::to_string(L.nx[2]) + "],\n \"variables\": [";
+  int rows = req.axes ? 1 : 0;
   for (size_t v = 0; v < codes.size(); ++v) {
     const int ns = field_var_is_dust(codes[v]) ? c.ns_dust : c.ns_gas;
     const std::string name = field_var_name(codes[v]);
@@ -294,77 +304,33 @@ std::string meta_json(const Clock &c, const FieldsLayout &L, const std::vector<i
       for (int d = 0; d < (field_var_is_vector(codes[v]) ? 3 : 1); ++d)
         j += std::string(n || d ? ", " : "") + json_str(name + "_" + std::to_string(n) + (field_var_is_vector(codes[v]) ? "_x" + std::to_string(d + 1) : ""));
     j += "]}";
+    rows += field_var_components(codes[v], c.ns_gas, c.ns_dust);
   }
-  if (reduce) j += ", {\"name\": \"volume\", \"ncomp\": 1, \"components\": [\"volume\"]}";
+  if (req.axes) j += ", {\"name\": \"volume\", \"ncomp\": 1, \"components\": [\"volume\"]}";
   j += "],\n \"blocks\": [";
-  int ncomp = 0;
-  for (const int code : codes) ncomp += field_var_components(code, c.ns_gas, c.ns_dust);
-  std::vector<long> offset(L.blocks.size(), 0); // version 2
-  if (level) {
-    std::vector<std::vector<size_t>> of_rank(static_cast<size_t>(L.nranks));
-    for (size_t g = 0; g < L.blocks.size(); ++g) of_rank[static_cast<size_t>(L.blocks[g].rank)].push_back(g);
-    for (std::vector<size_t> &gs : of_rank) {
-      std::sort(gs.begin(), gs.end(), [&](size_t a, size_t b) { return L.blocks[a].index < L.blocks[b].index; });
-      long at = 0;
-      for (const size_t g : gs) {
-        offset[g] = at;
-        const int s = L.blocks[g].level - *level;
-        at += static_cast<long>(ncomp) * level_extent(L.nx[0], s) * level_extent(L.nx[1], s) * level_extent(L.nx[2], s);
-      }
-    }
-  }
-  if (reduce && reduce_level) {
-    std::vector<std::vector<size_t>> of_rank(static_cast<size_t>(L.nranks));
-    for (size_t g = 0; g < L.blocks.size(); ++g) of_rank[static_cast<size_t>(L.blocks[g].rank)].push_back(g);
-    auto extent = [&](size_t g, int d) { return reduce_level_extent(L.nx[d], L.blocks[g].level - *reduce_level, reduce, d); };
-    for (std::vector<size_t> &gs : of_rank) {
-      std::sort(gs.begin(), gs.end(), [&](size_t a, size_t b) { return L.blocks[a].index < L.blocks[b].index; });
-      long at = 0;
-      for (const size_t g : gs) offset[g] = at, at += static_cast<long>(ncomp + 1) * extent(g, 0) * extent(g, 1) * extent(g, 2);
-    }
-    for (size_t g = 0; g < L.blocks.size(); ++g) {
-      const FieldBlock &B = L.blocks[g];
-      j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
-      for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
-      j += "], \"nx\": [" + std::to_string(extent(g, 0)) + ", " + std::to_string(extent(g, 1)) + ", " + std::to_string(extent(g, 2)) +
-           "], \"offset\": " + std::to_string(offset[g]) + ", \"rank\": " + std::to_string(B.rank) + ", \"index\": " + std::to_string(B.index) + "}";
-    }
-    return j + "]}\n";
-  }
-  if (reduce) {
-    const int o[3] = {(reduce & 1) ? 1 : L.nx[0], (reduce & 2) ? 1 : L.nx[1], (reduce & 4) ? 1 : L.nx[2]};
-    for (size_t g = 0; g < L.blocks.size(); ++g) {
-      const FieldBlock &B = L.blocks[g];
-      j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
-      for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
-      j += "], \"nx\": [" + std::to_string(o[0]) + ", " + std::to_string(o[1]) + ", " + std::to_string(o[2]) + "], \"offset\": " +
-           std::to_string(static_cast<long>(B.index) * (ncomp + 1) * o[0] * o[1] * o[2]) + ", \"rank\": " + std::to_string(B.rank) +
-           ", \"index\": " + std::to_string(B.index) + "}";
-    }
-    return j + "]}\n";
+  auto extent = [&](size_t g, int d) { return reduce_level_extent(L.nx[d], req.has_level ? L.blocks[g].level - req.level : 0, req.axes, d); };
+  std::vector<long> offset(L.blocks.size(), 0);
+  std::vector<std::vector<size_t>> of_rank(static_cast<size_t>(L.nranks));
+  for (size_t g = 0; g < L.blocks.size(); ++g) of_rank[static_cast<size_t>(L.blocks[g].rank)].push_back(g);
+  for (std::vector<size_t> &gs : of_rank) {
+    std::sort(gs.begin(), gs.end(), [&](size_t a, size_t b) { return L.blocks[a].index < L.blocks[b].index; });
+    long at = 0;
+    for (const size_t g : gs) offset[g] = at, at += static_cast<long>(rows) * extent(g, 0) * extent(g, 1) * extent(g, 2);
   }
   for (size_t g = 0; g < L.blocks.size(); ++g) {
     const FieldBlock &B = L.blocks[g];
-    if (level) {
-      const int s = B.level - *level;
-      j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
-      for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
-      j += "], \"nx\": [" + std::to_string(level_extent(L.nx[0], s)) + ", " + std::to_string(level_extent(L.nx[1], s)) + ", " +
-           std::to_string(level_extent(L.nx[2], s)) + "], \"offset\": " + std::to_string(offset[g]) + ", \"rank\": " + std::to_string(B.rank) +
-           ", \"index\": " + std::to_string(B.index) + "}";
-      continue;
-    }
     j += std::string(g ? ",\n  " : "\n  ") + "{\"gid\": " + std::to_string(B.gid) + ", \"level\": " + std::to_string(B.level) + ", \"bounds\": [";
     for (int q = 0; q < 6; ++q) j += (q ? ", " : "") + json_num(B.bounds[q]);
-    j += "], \"nx\": " + nx + ", \"rank\": " + std::to_string(B.rank) + ", \"index\": " + std::to_string(B.index) + "}";
+    j += "], \"nx\": [" + std::to_string(extent(g, 0)) + ", " + std::to_string(extent(g, 1)) + ", " + std::to_string(extent(g, 2)) + "]" +
+         (version > 1 ? ", \"offset\": " + std::to_string(offset[g]) : std::string()) + ", \"rank\": " + std::to_string(B.rank) +
+         ", \"index\": " + std::to_string(B.index) + "}";
   }
   return j + "]}\n";
 }
 
-// One field dump (artemis_driver.h: artemis_sim_write_fields).  Every rank takes every vote, whatever happened to it
+// One field dump (artemis_driver.h: artemis_sim_write_fields*).  Every rank takes every vote, whatever happened to it
 // before: the votes are collective.
-void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vector<int> &codes, bool single, const int *level = nullptr,
-                  int reduce = 0, const int *reduce_level = nullptr) {
+void write_fields(artemis_sim_t *sim, const std::string &path_in, const FieldRequest &req) {
   std::string err, dir = path_in, tmp;
   while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
   tmp = dir + ".tmp";
@@ -373,7 +339,7 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   try {
     const std::string dead = artemis_ckpt::dead_reason(sim);
     if (!dead.empty()) throw std::runtime_error(dead);
-    if (codes.empty()) throw std::runtime_error("no variables");
+    if (req.codes.empty()) throw std::runtime_error("no variables");
     L = fields_layout(sim);
     if (c.rank == 0) {
       remove_field_dir(tmp);
@@ -385,14 +351,8 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   bool failed = vote(sim, !err.empty());
   if (!failed) {
     try {
-      std::vector<char> host(reduce && reduce_level ? gather_fields_reduced_level(sim, codes, single, reduce, *reduce_level, nullptr, nullptr)
-                             : reduce ? gather_fields_reduced(sim, codes, single, reduce, nullptr)
-                             : level ? gather_fields_level(sim, codes, single, *level, nullptr, nullptr)
-                                     : gather_fields(sim, codes, single, nullptr));
-      if (reduce && reduce_level) gather_fields_reduced_level(sim, codes, single, reduce, *reduce_level, host.data(), nullptr);
-      else if (reduce) gather_fields_reduced(sim, codes, single, reduce, host.data());
-      else if (level) gather_fields_level(sim, codes, single, *level, host.data(), nullptr);
-      else gather_fields(sim, codes, single, host.data());
+      std::vector<char> host(gather_fields(sim, req, nullptr, nullptr));
+      gather_fields(sim, req, host.data(), nullptr);
       write_file(tmp + "/rank" + std::to_string(c.rank) + ".bin", host.data(), host.size());
     } catch (const std::exception &e) {
       err = e.what();
@@ -402,7 +362,7 @@ void write_fields(artemis_sim_t *sim, const std::string &path_in, const std::vec
   if (!failed) {
     try {
       if (c.rank == 0) {
-        const std::string meta = meta_json(c, L, codes, single, level, reduce, reduce_level);
+        const std::string meta = meta_json(c, L, req);
         write_file(tmp + "/meta.json", meta.data(), meta.size()); // last: a directory with it has all its parts
         remove_field_dir(dir);
         if (std::rename(tmp.c_str(), dir.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + dir + ": " + std::strerror(errno));
@@ -426,7 +386,7 @@ void write_field_dump(artemis_sim_t *sim, State &st, OutBlock &b, bool final) {
   char num[16];
   std::snprintf(num, sizeof num, "%05ld", b.counter);
   b.path = st.dir + "/" + st.problem_id + ".out" + std::to_string(b.index) + "." + (final ? std::string("final") : std::string(num)) + ".fld";
-  write_fields(sim, b.path, b.codes, b.single, b.has_level ? &b.level : nullptr, b.reduce, b.has_reduce_level ? &b.reduce_level : nullptr);
+  write_fields(sim, b.path, request_of(b));
   if (!final) b.counter++;
 }
 
@@ -514,90 +474,41 @@ int artemis_sim_enable_outputs(artemis_sim_t *sim, const char *dir) {
   }
 }
 
-int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single) {
+// The artemis_sim_write_fields* entry points: the names become the codes of `req`, then the dump
+static int write_entry(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, artemis_out::FieldRequest req) {
   using namespace artemis_out;
   try {
     if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
     const Clock c = clock_of(sim);
-    std::vector<int> codes;
     for (int v = 0; v < nvar; ++v) {
       const std::string name = (names && names[v]) ? names[v] : "";
       const int code = field_var_code(name);
       if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
-      codes.push_back(code);
+      req.codes.push_back(code);
     }
-    write_fields(sim, path, codes, single != 0);
-    return 0;
-  } catch (const std::exception &e) {
-    artemis_ckpt::set_error(e.what());
-    return 1;
-  }
-}
-
-int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int level) {
-  using namespace artemis_out;
-  try {
-    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
-    const Clock c = clock_of(sim);
-    std::vector<int> codes;
-    for (int v = 0; v < nvar; ++v) {
-      const std::string name = (names && names[v]) ? names[v] : "";
-      const int code = field_var_code(name);
-      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
-      codes.push_back(code);
-    }
-    write_fields(sim, path, codes, single != 0, &level);
-    return 0;
-  } catch (const std::exception &e) {
-    artemis_ckpt::set_error(e.what());
-    return 1;
-  }
-}
-
-int artemis_sim_write_fields_reduced(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes) {
-  using namespace artemis_out;
-  try {
-    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
-    const Clock c = clock_of(sim);
-    std::vector<int> codes;
-    for (int v = 0; v < nvar; ++v) {
-      const std::string name = (names && names[v]) ? names[v] : "";
-      const int code = field_var_code(name);
-      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
-      codes.push_back(code);
-    }
-    const std::string rule = reduce_rule(axes, c.mbnx); // (every rank holds blocks of the same shape: all refuse or none)
+    // (every rank holds blocks of the same shape: all refuse the axes or none.  A shift that breaks a rule throws inside
+    //  the gather, on the ranks that hold such a block, and the vote spreads it)
+    const std::string rule = req.axes ? reduce_rule(req.axes, c.mbnx) : "";
     if (!rule.empty()) throw std::runtime_error("write_fields: " + rule);
-    write_fields(sim, path, codes, single != 0, nullptr, axes);
+    write_fields(sim, path, req);
     return 0;
   } catch (const std::exception &e) {
     artemis_ckpt::set_error(e.what());
     return 1;
   }
 }
-
+int artemis_sim_write_fields(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single) {
+  return write_entry(sim, path, nvar, names, {{}, single != 0, 0, false, 0});
+}
+int artemis_sim_write_fields_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int level) {
+  return write_entry(sim, path, nvar, names, {{}, single != 0, 0, true, level});
+}
+int artemis_sim_write_fields_reduced(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes) {
+  return write_entry(sim, path, nvar, names, {{}, single != 0, artemis_out::reducing_axes(axes), false, 0});
+}
 int artemis_sim_write_fields_reduced_level(artemis_sim_t *sim, const char *path, int nvar, const char *const *names, int single, int axes,
                                            int level) {
-  using namespace artemis_out;
-  try {
-    if (!sim || !path || !*path) throw std::runtime_error("write_fields: no simulation or no path");
-    const Clock c = clock_of(sim);
-    std::vector<int> codes;
-    for (int v = 0; v < nvar; ++v) {
-      const std::string name = (names && names[v]) ? names[v] : "";
-      const int code = field_var_code(name);
-      if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("write_fields: unknown variable " + name);
-      codes.push_back(code);
-    }
-    const std::string rule = reduce_rule(axes, c.mbnx); // (every rank holds blocks of the same shape: all refuse or none)
-    if (!rule.empty()) throw std::runtime_error("write_fields: " + rule);
-    // (a shift that breaks a rule throws inside the gather, on the ranks that hold such a block, and the vote spreads it)
-    write_fields(sim, path, codes, single != 0, nullptr, axes, &level);
-    return 0;
-  } catch (const std::exception &e) {
-    artemis_ckpt::set_error(e.what());
-    return 1;
-  }
+  return write_entry(sim, path, nvar, names, {{}, single != 0, artemis_out::reducing_axes(axes), true, level});
 }
 
 long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in, double time) {

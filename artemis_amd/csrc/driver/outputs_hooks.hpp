@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "artemis_driver.h"
+#include "../fields_shape.hpp"
 
 namespace artemis_out {
 
@@ -63,28 +64,22 @@ struct FieldsLayout {
 };
 // (driver.cpp) the global block table: every rank contributes its rows (collective)
 FieldsLayout fields_layout(artemis_sim_t *sim);
-// (driver.cpp) this rank's blocks as [local block][component][nk][nj][ni] of interior zones, double or float: through
-// artemis_hip_pack_fields and a bounded staging buffer, or -- a library without that kernel -- a host loop over the
-// downloaded primitives.  host_out = NULL: nothing is gathered.  Returns the bytes of the gather.
-size_t gather_fields(artemis_sim_t *sim, const std::vector<int> &codes, bool single, void *host_out);
-// ---- ... at a refinement level: a block on level l asked for level L has shift s = l - L; s >= 1 restricts it s times
-// (volume-weighted), s <= -1 replicates its zones, along the ACTIVE directions (more than one zone) only
-constexpr int kMaxShift = 3;
-inline int level_extent(int n, int shift) { return n == 1 ? 1 : (shift >= 0 ? n >> shift : n << -shift); }
-// "" or the rule a block of nx zones breaks at this shift
-inline std::string level_rule(int shift, const int nx[3]) {
-  if (shift > kMaxShift || shift < -kMaxShift) return "would need shift " + std::to_string(shift) + ", |shift| <= 3 is built";
-  for (int d = 0; d < 3; ++d)
-    if (shift > 0 && nx[d] > 1 && nx[d] % (1 << shift) != 0)
-      return "would need shift " + std::to_string(shift) + ", and its nx" + std::to_string(d + 1) + " = " + std::to_string(nx[d]) +
-             " is not divisible by " + std::to_string(1 << shift);
-  return "";
-}
-// (driver.cpp) the gather with every block on the zone size of `level`, the blocks one after the other, each
-// [component][nk'][nj'][ni']; offsets (nblocks_local + 1 longs, or null): element offset of every block and the total.
-// host_out = NULL: sizes only.  Throws, before anything is written, for a block whose shift breaks a rule.
-size_t gather_fields_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int level, void *host_out, long *offsets);
-// ---- ... integrated over chosen directions: `axes` is a mask, bit 0 x1, bit 1 x2, bit 2 x3, of ACTIVE directions
+// ---- one request for every mode of a gather: two independent choices.  axes (a mask, bit 0 x1, bit 1 x2, bit 2 x3, of
+// ACTIVE directions; 0: none): every block integrated over them -- per component the sum of V q, and the volume as one
+// more, last, row.  level: a block on level l has shift s = l - level; s >= 1 brings it down s times, s <= -1 up, along
+// the ACTIVE directions (more than one zone) it keeps -- means by the volume-weighted restriction or by replication,
+// integrals by pair sums or by an even share (artemis_hip.h, artemis_hip_pack_fields_level and _reduce_fields_level).
+struct FieldRequest {
+  std::vector<int> codes; // enum artemis_field_var
+  bool single = false;
+  int axes = 0;
+  bool has_level = false;
+  int level = 0;
+};
+// the mask of an entry point that always reduces: its 0 is not "none" but an empty mask, which reduce_rule refuses like
+// every other mask outside 1 .. 7
+inline int reducing_axes(int axes) { return axes ? axes : -1; }
+using artemis_fields::reduce_level_extent;
 // "" or what is wrong with a list "x2,x3" (axes filled: the mask)
 inline std::string reduce_parse(const std::string &list, int &axes) {
   axes = 0;
@@ -104,28 +99,20 @@ inline std::string reduce_parse(const std::string &list, int &axes) {
 }
 // "" or the rule a block of nx zones breaks with these axes
 inline std::string reduce_rule(int axes, const int nx[3]) {
-  if (axes < 1 || axes > 7) return "reduce: no direction";
-  for (int d = 0; d < 3; ++d)
-    if (((axes >> d) & 1) && nx[d] < 2) return "reduce: x" + std::to_string(d + 1) + " has one zone and is not a direction to reduce";
-  return "";
+  const std::string bad = artemis_fields::axes_rule(axes, nx, "no direction");
+  return bad.empty() ? bad : "reduce: " + bad;
 }
-// (driver.cpp) the gather with every block integrated over `axes`: [local block][component, the volume last][nk'][nj'][ni']
-// with the reduced extents 1.  host_out = NULL: the size only.  Throws, before anything is written, where reduce_rule does.
-size_t gather_fields_reduced(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, void *host_out);
-// ---- ... and brought to a refinement level along the KEPT directions (active, outside axes): artemis_hip.h,
-// artemis_hip_reduce_fields_level, has the definition.  A reduced extent is 1 at every shift.
-inline int reduce_level_extent(int n, int shift, int axes, int d) { return ((axes >> d) & 1) ? 1 : level_extent(n, shift); }
-// "" or the rule a block of nx zones breaks at this shift with these axes: level_rule on the kept extents
-inline std::string reduce_level_rule(int shift, int axes, const int nx[3]) {
-  const int kept[3] = {(axes & 1) ? 1 : nx[0], (axes & 2) ? 1 : nx[1], (axes & 4) ? 1 : nx[2]};
-  return level_rule(shift, kept);
+// "" or the rule a block of nx zones breaks at this shift along the directions these axes (0: none) keep
+inline std::string level_rule(int shift, int axes, const int nx[3]) {
+  const std::string bad = artemis_fields::shift_rule(shift, axes, nx);
+  return bad.empty() ? bad : "would need " + bad;
 }
-// (driver.cpp) the reduced gather with every block on the zone size of `level` along the kept directions, the blocks one
-// after the other, each [component, the volume last][nk'][nj'][ni']; offsets (nblocks_local + 1 longs, or null): element
-// offset of every block and the total.  host_out = NULL: sizes only.  Throws, before anything is written, where
-// reduce_rule or -- for any block -- reduce_level_rule does.
-size_t gather_fields_reduced_level(artemis_sim_t *sim, const std::vector<int> &codes, bool single, int axes, int level, void *host_out,
-                                   long *offsets);
+// (driver.cpp) this rank's blocks one after the other, block b as [rows][nk'][nj'][ni'] of interior zones, double or float,
+// rows = the components, and the volume where axes are set: through the artemis_hip_* entry point of the mode and a
+// bounded staging buffer, or -- a library without that kernel -- a host loop over the downloaded primitives.  offsets
+// (nblocks_local + 1 longs, or null): element offset of every block and the total.  host_out = NULL: sizes only.  Throws,
+// before anything is written, where reduce_rule or -- for any block -- level_rule does.  Returns the bytes of the gather.
+size_t gather_fields(artemis_sim_t *sim, const FieldRequest &req, void *host_out, long *offsets);
 // (driver.cpp) the inverse: host_in in that layout, holding one complete form of the state per fluid (csrc/fields_form.hpp),
 // becomes the interior primitives of the current buffer -- artemis_hip_unpack_fields out of the same staging buffer, or the
 // host loop -- and the state is completed as a problem generator's is; time = NaN keeps the clock, dt is estimated afresh.

@@ -542,6 +542,16 @@ class Simulation:
             raise ValueError("reduce_level together with level is not built: level resamples means, reduce_level integrals")
         return int(reduce_level)
 
+    @classmethod
+    def _field_mode(cls, level, reduce, reduce_level):
+        """The two choices of gather / write_fields resolved: (suffix of the C entry point's name, its arguments after
+        `single`, the mask of reduce or 0, the level the blocks are brought to or None)"""
+        rl = cls._reduce_level(reduce, level, reduce_level)
+        axes = 0 if reduce is None else cls._axes(reduce, level)
+        lv = rl if axes else (None if level is None else int(level))
+        return (("_reduced" if axes else "") + ("" if lv is None else "_level"), ([axes] if axes else []) + ([] if lv is None else [lv]),
+                axes, lv)
+
     def gather(self, variables, single=False, level=None, reduce=None, reduce_level=None):
         """The named variables ('gas.prim.density', 'gas.prim.velocity', 'gas.prim.pressure', ...: include/artemis_driver.h
         "field output") of this rank's blocks, interior zones only, as [nblocks_local, ncomp, nz, ny, nx] float64 (float32
@@ -562,64 +572,26 @@ class Simulation:
         All blocks then share a zone size, so those of a refined mesh add cell by cell.  reduce_level without reduce, or
         with level, raises ValueError."""
         names, n = self._names(variables)
-        rl = self._reduce_level(reduce, level, reduce_level)
-        if rl is not None:
-            axes = self._axes(reduce, level)
-            self._refresh_dims()
-            off = (C.c_long * (self.nblocks + 1))()
-            nbytes = self.L.artemis_sim_gather_fields_reduced_level(self.h, n, names, int(single), axes, rl, None, off)
-            if nbytes < 0:
-                raise RuntimeError(self.L.artemis_sim_last_error().decode())
-            out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
-            ncomp = self.L.artemis_sim_gather_fields_reduced_level(self.h, n, names, int(single), axes, rl, out.ctypes.data, off)
-            if ncomp < 0:
-                raise RuntimeError(self.L.artemis_sim_last_error().decode())
-            nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
-            blocks = []
-            for b in range(self.nblocks):
-                s = self.block_level(b) - rl
-                shape = [1 if (axes >> q) & 1 or m == 1 else (m >> s if s >= 0 else m << -s) for q, m in enumerate(nx)]
-                blocks.append(out[off[b]:off[b + 1]].reshape(ncomp + 1, shape[2], shape[1], shape[0]))
-            return blocks
-        if reduce is not None:
-            axes = self._axes(reduce, level)
-            nbytes = self.L.artemis_sim_gather_fields_reduced(self.h, n, names, int(single), axes, None)
-            if nbytes < 0:
-                raise RuntimeError(self.L.artemis_sim_last_error().decode())
-            self._refresh_dims()
-            out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
-            ncomp = self.L.artemis_sim_gather_fields_reduced(self.h, n, names, int(single), axes, out.ctypes.data)
-            if ncomp < 0:
-                raise RuntimeError(self.L.artemis_sim_last_error().decode())
-            nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
-            shape = [1 if (axes >> q) & 1 else nx[q] for q in range(3)]
-            return out.reshape(self.nblocks, ncomp + 1, shape[2], shape[1], shape[0])
-        if level is not None:
-            self._refresh_dims()
-            off = (C.c_long * (self.nblocks + 1))()
-            nbytes = self.L.artemis_sim_gather_fields_level(self.h, n, names, int(single), int(level), None, off)
-            if nbytes < 0:
-                raise RuntimeError(self.L.artemis_sim_last_error().decode())
-            out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
-            ncomp = self.L.artemis_sim_gather_fields_level(self.h, n, names, int(single), int(level), out.ctypes.data, off)
-            if ncomp < 0:
-                raise RuntimeError(self.L.artemis_sim_last_error().decode())
-            nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
-            blocks = []
-            for b in range(self.nblocks):
-                s = self.block_level(b) - int(level)
-                shape = [m if m == 1 else (m >> s if s >= 0 else m << -s) for m in nx]
-                blocks.append(out[off[b]:off[b + 1]].reshape(ncomp, shape[2], shape[1], shape[0]))
-            return blocks
-        nbytes = self.L.artemis_sim_gather_fields(self.h, n, names, int(single), None)
+        suffix, args, axes, lv = self._field_mode(level, reduce, reduce_level)
+        fn = getattr(self.L, "artemis_sim_gather_fields" + suffix)
+        self._refresh_dims()
+        off = (C.c_long * (self.nblocks + 1))()
+        tail = [] if lv is None else [off]
+        nbytes = fn(self.h, n, names, int(single), *args, None, *tail)
         if nbytes < 0:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
-        self._refresh_dims()
         out = np.empty(nbytes // (4 if single else 8), dtype=np.float32 if single else np.float64)
-        ncomp = self.L.artemis_sim_gather_fields(self.h, n, names, int(single), out.ctypes.data)
+        ncomp = fn(self.h, n, names, int(single), *args, out.ctypes.data, *tail)
         if ncomp < 0:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
-        return out.reshape(self.nblocks, ncomp, self.ke - self.ks + 1, self.je - self.js + 1, self.ie - self.is_ + 1)
+        nx = [self.ie - self.is_ + 1, self.je - self.js + 1, self.ke - self.ks + 1]
+
+        def shape(s):  # of a block at shift s: the rows (the volume last where axes are set), then nz', ny', nx'
+            e = [1 if (axes >> q) & 1 or m == 1 else (m >> s if s >= 0 else m << -s) for q, m in enumerate(nx)]
+            return (ncomp + (1 if axes else 0), e[2], e[1], e[0])
+        if lv is None:
+            return out.reshape((self.nblocks,) + shape(0))
+        return [out[off[b]:off[b + 1]].reshape(shape(self.block_level(b) - lv)) for b in range(self.nblocks)]
 
     def write_fields(self, path, variables, single=False, level=None, reduce=None, reduce_level=None):
         """One dump of the named variables as a directory at `path` (collective over the ranks of the run; replaces an
@@ -629,17 +601,9 @@ class Simulation:
         reduce_level = an int beside reduce: the reduced blocks brought to that level along their kept directions as in gather
         (a version-4 dump, which FieldDump.reduced() assembles on any mesh)."""
         names, n = self._names(variables)
-        rl = self._reduce_level(reduce, level, reduce_level)
-        if rl is not None:
-            rc = self.L.artemis_sim_write_fields_reduced_level(self.h, os.fspath(path).encode(), n, names, int(single),
-                                                               self._axes(reduce, level), rl)
-        elif reduce is not None:
-            rc = self.L.artemis_sim_write_fields_reduced(self.h, os.fspath(path).encode(), n, names, int(single), self._axes(reduce, level))
-        elif level is None:
-            rc = self.L.artemis_sim_write_fields(self.h, os.fspath(path).encode(), n, names, int(single))
-        else:
-            rc = self.L.artemis_sim_write_fields_level(self.h, os.fspath(path).encode(), n, names, int(single), int(level))
-        if rc:
+        suffix, args, _, _ = self._field_mode(level, reduce, reduce_level)
+        fn = getattr(self.L, "artemis_sim_write_fields" + suffix)
+        if fn(self.h, os.fspath(path).encode(), n, names, int(single), *args):
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
 
     def scatter(self, variables, array, time=None):
