@@ -39,6 +39,10 @@ FIELD_VARS = ("gas.prim.density", "gas.prim.velocity", "gas.prim.pressure", "gas
               "gas.cons.momentum", "gas.cons.total_energy", "gas.cons.internal_energy", "dust.prim.density",
               "dust.prim.velocity", "dust.cons.density", "dust.cons.momentum")
 FIELD_VAR = {name: code for code, name in enumerate(FIELD_VARS)}
+# ... and the derived variables, outputs only and a second range of codes (ARTEMIS_VAR_DERIVED0): formed from a zone and its
+# face neighbours, 1 (divergence) or 3 (vorticity) components per species
+DERIVED_FIELD_VAR = {"gas.derived.divergence": 16, "gas.derived.vorticity": 17, "dust.derived.divergence": 18,
+                     "dust.derived.vorticity": 19}
 RSOLVER = {"hllc": HLLC, "hlle": HLLE, "llf": LLF}
 RECON = {"pcm": PCM, "plm": PLM, "ppm": PPM}
 BCS = {"periodic": BC_PERIODIC, "outflow": BC_OUTFLOW, "reflecting": BC_REFLECT,

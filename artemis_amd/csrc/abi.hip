@@ -264,14 +264,17 @@ static const char *field_selection(const artemis_pack_t *p, int nsel, const int 
   if (nsel < 0 || nsel > artemis::FIELDS_MAX_SEL || (nsel > 0 && !sel)) return "pack fields: 0 to 32 variable codes are taken";
   for (int e = 0; e < nsel; ++e) {
     const int code = sel[e];
-    if (code < 0 || code >= ARTEMIS_VAR_COUNT) return "pack fields: unknown variable code";
-    const bool dust = code >= ARTEMIS_VAR_DUST_PRIM_DENSITY;
+    const bool derived = code >= ARTEMIS_VAR_DERIVED0 && code < ARTEMIS_VAR_DERIVED_END; // (a second range: 12 .. 15 are no codes)
+    if ((code < 0 || code >= ARTEMIS_VAR_COUNT) && !derived) return "pack fields: unknown variable code";
+    const bool dust = derived ? code >= ARTEMIS_VAR_DUST_DERIVED_DIVERGENCE : code >= ARTEMIS_VAR_DUST_PRIM_DENSITY;
     const int ns = dust ? p->dust.nspecies : p->gas.nspecies;
     if (ns < 1) return dust ? "pack fields: a dust variable on a pack without dust" : "pack fields: a gas variable on a pack without gas";
     const bool vec = code == ARTEMIS_VAR_GAS_PRIM_VELOCITY || code == ARTEMIS_VAR_GAS_CONS_MOMENTUM ||
-                     code == ARTEMIS_VAR_DUST_PRIM_VELOCITY || code == ARTEMIS_VAR_DUST_CONS_MOMENTUM;
+                     code == ARTEMIS_VAR_DUST_PRIM_VELOCITY || code == ARTEMIS_VAR_DUST_CONS_MOMENTUM ||
+                     code == ARTEMIS_VAR_GAS_DERIVED_VORTICITY || code == ARTEMIS_VAR_DUST_DERIVED_VORTICITY;
     S.code[e] = code, S.comp0[e] = S.ncomp, S.ncomp += (vec ? 3 : 1) * ns;
-    (dust ? S.want_dust : S.want_gas) = 1;
+    // (want_*: the fluids the plain pass loads; the derived codes have a pass of their own: field_passes, kernels.hpp)
+    if (!derived) (dust ? S.want_dust : S.want_gas) = 1;
   }
   S.nsel = nsel;
   return "";
@@ -304,7 +307,9 @@ static std::string fields_plan(const FieldsMode &M, const artemis_pack_t *p, int
   if (nblocks < 0 || block0 < 0 || block0 > p->nblocks || nblocks > p->nblocks - block0)
     return who + "blocks [" + std::to_string(block0) + ", " + std::to_string(block0) + " + " + std::to_string(nblocks) +
            ") are not inside the pack's " + std::to_string(p->nblocks);
-  if (launch && ((P.F.want_gas && !p->gas.prim) || (P.F.want_dust && !p->dust.prim)))
+  const artemis::FieldPasses X = artemis::field_passes(P.F);
+  const bool need_gas = X.plain.want_gas || X.derived.want_gas, need_dust = X.plain.want_dust || X.derived.want_dust;
+  if (launch && ((need_gas && !p->gas.prim) || (need_dust && !p->dust.prim)))
     return who + "the primitive tables of the fluids asked for are required";
   const int nx[3] = {p->nx1, p->nx2, p->nx3};
   if (M.axes) {

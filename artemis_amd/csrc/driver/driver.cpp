@@ -28,6 +28,7 @@
 #include "artemis_hip.h"
 #include "artemis_rt.h"
 #include "../geometry_core.hpp"
+#include "../fields_derived.hpp"
 #include "../fields_form.hpp"
 #include "parameter_input.hpp"
 #include "block_tree.hpp"
@@ -60,6 +61,8 @@ extern "C" size_t artemis_hip_reduce_fields_level_work_bytes(const artemis_pack_
 extern "C" int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                                          const void *in_dev, void *stream) __attribute__((weak));
 static_assert(artemis_out::kFieldVars == ARTEMIS_VAR_COUNT, "outputs_hooks.hpp names every artemis_field_var");
+static_assert(artemis_out::kDerived0 == ARTEMIS_VAR_DERIVED0 && artemis_out::kDerivedEnd == ARTEMIS_VAR_DERIVED_END,
+              "outputs_hooks.hpp names every derived artemis_field_var");
 
 #define SQR(x) ((x) * (x))
 typedef double Real;
@@ -3551,6 +3554,10 @@ void artemis_sim_impl::host_block_components(int b, const std::vector<int> &code
   std::vector<Real> g, d;
   if (nsg) g = download(gprim[base], b);
   if (nsd) d = download(dprim[base], b);
+  bool derived = false;
+  for (const int code : codes) derived = derived || artemis_out::field_var_is_derived(code);
+  const bool act[3] = {mbnx[0] > 1, mbnx[1] > 1, mbnx[2] > 1};
+  const long st[3] = {1, ni, static_cast<long>(ni) * nj};
   for (int k = ks; k <= ke; ++k)
     for (int j = js; j <= je; ++j)
       for (int i = is; i <= ie; ++i) {
@@ -3558,6 +3565,19 @@ void artemis_sim_impl::host_block_components(int b, const std::vector<int> &code
         const size_t z = (static_cast<size_t>(k - ks) * mbnx[1] + (j - js)) * mbnx[0] + (i - is);
         auto put = [&](int comp, Real v) { vals[comp * zones + z] = v; };
         if (vol) (*vol)[z] = cell_coords(b, k, j, i).volume();
+        // the derived variables: load_derived's stencil (fields_device.hpp) on the downloaded block, ghost zones and all
+        auto put_derived = [&](const std::vector<Real> &w, int ns, int n, int code0) {
+          const artemis::DerivedZone dz = artemis::derived_zone(
+              coords != ARTEMIS_CARTESIAN, act, [&](int q, int a, int s) { return w[(ns + 3 * n + q) * N + c + s * st[a]]; },
+              [&](int a, int s) { return cell_coords(b, k + (a == 2 ? s : 0), j + (a == 1 ? s : 0), i + (a == 0 ? s : 0)); });
+          for (size_t e = 0; e < codes.size(); ++e) {
+            if (codes[e] == code0) put(comp0[e] + n, dz.div);
+            else if (codes[e] == code0 + 1)
+              for (int q = 0; q < 3; ++q) put(comp0[e] + 3 * n + q, dz.w[q]);
+          }
+        };
+        for (int n = 0; n < (derived ? nsg : 0); ++n) put_derived(g, nsg, n, ARTEMIS_VAR_GAS_DERIVED_DIVERGENCE);
+        for (int m = 0; m < (derived ? nsd : 0); ++m) put_derived(d, nsd, m, ARTEMIS_VAR_DUST_DERIVED_DIVERGENCE);
         Real hx[3] = {1.0, 1.0, 1.0}; // GetScaleFactors (geometry.hpp:384-388)
         if (coords != ARTEMIS_CARTESIAN) {
           const artemis::DCoords co = cell_coords(b, k, j, i);
@@ -3623,8 +3643,9 @@ FieldPlan artemis_sim_impl::plan_fields(const artemis_out::FieldRequest &req) {
   const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
   FieldPlan P;
   for (const int code : req.codes) {
-    const int n = (code >= 0 && code < artemis_out::kFieldVars) ? artemis_out::field_var_components(code, nsg, nsd) : 0;
-    if (n == 0) throw std::runtime_error("fields: unknown variable " + (code >= 0 && code < artemis_out::kFieldVars ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
+    const bool known = artemis_out::field_var_known(code);
+    const int n = known ? artemis_out::field_var_components(code, nsg, nsd) : 0;
+    if (n == 0) throw std::runtime_error("fields: unknown variable " + (known ? std::string(artemis_out::field_var_name(code)) : "code " + std::to_string(code)));
     P.comp0.push_back(P.ncomp), P.ncomp += n;
   }
   if (P.ncomp == 0 && (req.axes || req.has_level)) throw std::runtime_error("fields: no variables");
@@ -3658,6 +3679,11 @@ size_t artemis_sim_impl::gather_fields(const artemis_out::FieldRequest &req, voi
   if (offsets) std::copy(off.begin(), off.end(), offsets);
   const size_t esz = req.single ? sizeof(float) : sizeof(double), total = static_cast<size_t>(off[nb]) * esz;
   if (!host_out || total == 0) return total;
+  // A derived variable reads the face neighbours of a zone: the ghost zones a stage loop left for later are filled first.
+  // That writes ghost zones only, which no stage kernel of such a loop reads: the run's bits do not move.
+  bool derived = false;
+  for (const int code : req.codes) derived = derived || artemis_out::field_var_is_derived(code);
+  if (derived) fill_stale_ghosts();
   const int nsel = static_cast<int>(req.codes.size()), single = req.single ? 1 : 0, axes = req.axes;
   const int *sel = req.codes.data();
   const bool device = axes ? (req.has_level ? artemis_hip_reduce_fields_level && artemis_hip_reduce_fields_level_work_bytes

@@ -522,6 +522,7 @@ long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const 
     for (int v = 0; v < nvar; ++v) {
       const std::string name = (names && names[v]) ? names[v] : "";
       const int code = field_var_code(name);
+      if (code >= 0 && field_var_is_derived(code)) throw std::runtime_error("scatter_fields: " + name + " is an output, not part of a state");
       if (code < 0 || field_var_components(code, c.ns_gas, c.ns_dust) == 0) throw std::runtime_error("scatter_fields: unknown variable " + name);
       codes.push_back(code);
     }

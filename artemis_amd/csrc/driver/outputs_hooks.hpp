@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "artemis_driver.h"
+#include "../fields_form.hpp"
 #include "../fields_shape.hpp"
 
 namespace artemis_out {
@@ -30,22 +31,26 @@ const State *state_of(const artemis_sim_t *sim);
 int history_sums(artemis_sim_t *sim, double *out);
 
 // ---- field output ----------------------------------------------------------------------------------------------------
-// The variables a `fld` block may name, in the order of enum artemis_field_var (include/artemis_hip.h)
-constexpr int kFieldVars = 12;
+// The variables a `fld` block may name: those of enum artemis_field_var (include/artemis_hip.h) in its order, and the derived
+// ones -- outputs only, formed from a zone and its face neighbours -- at their codes, a second range
+constexpr int kFieldVars = 12, kDerived0 = 16, kDerivedEnd = 20;
+inline bool field_var_known(int code) { return (code >= 0 && code < kFieldVars) || (code >= kDerived0 && code < kDerivedEnd); }
+inline bool field_var_is_derived(int code) { return code >= kDerived0 && code < kDerivedEnd; }
 inline const char *field_var_name(int code) {
   static const char *const names[kFieldVars] = {"gas.prim.density", "gas.prim.velocity", "gas.prim.pressure", "gas.prim.sie",
                                                 "gas.cons.density", "gas.cons.momentum", "gas.cons.total_energy",
                                                 "gas.cons.internal_energy", "dust.prim.density", "dust.prim.velocity",
                                                 "dust.cons.density", "dust.cons.momentum"};
+  if (field_var_is_derived(code)) return artemis::field_var_text(code); // (fields_form.hpp has the one copy of these names)
   return (code >= 0 && code < kFieldVars) ? names[code] : "";
 }
 inline int field_var_code(const std::string &name) { // -1: no such variable
-  for (int c = 0; c < kFieldVars; ++c)
-    if (name == field_var_name(c)) return c;
+  for (int c = 0; c < kDerivedEnd; ++c)
+    if (field_var_known(c) && name == field_var_name(c)) return c;
   return -1;
 }
-inline bool field_var_is_dust(int code) { return code >= 8; }
-inline bool field_var_is_vector(int code) { return code == 1 || code == 5 || code == 9 || code == 11; }
+inline bool field_var_is_dust(int code) { return field_var_is_derived(code) ? code >= 18 : code >= 8; }
+inline bool field_var_is_vector(int code) { return code == 1 || code == 5 || code == 9 || code == 11 || code == 17 || code == 19; }
 // components of a variable on a run with these species counts; 0: its fluid is absent
 inline int field_var_components(int code, int ns_gas, int ns_dust) {
   return (field_var_is_vector(code) ? 3 : 1) * (field_var_is_dust(code) ? ns_dust : ns_gas);

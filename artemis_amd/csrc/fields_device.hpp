@@ -4,6 +4,7 @@
 // averages and what the reduce kernel integrates are the same doubles.
 #pragma once
 #include "device_math.hpp"
+#include "fields_derived.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
 #include "pack_view.hpp"
@@ -80,6 +81,25 @@ __device__ __forceinline__ void dust_components(const DustZone &z, const double 
   }
 }
 
+// The derived variables of one species at zone (k, j, i) (fields_derived.hpp: the stencil of the six face neighbours, plain
+// 8-byte loads of the stored velocities -- the x1 neighbours in lines the wave or its tile neighbour fetches anyway, the
+// x2 / x3 neighbours in rows the tile above or below fetches) and their components, as gas_components hands them out
+template <bool CURV, bool GAS>
+__device__ __forceinline__ DerivedZone load_derived(const PackView &P, int b, int n, int k, int j, int i) {
+  const FluidView &f = GAS ? P.gas : P.dust;
+  const int ns = f.ns, v1 = b * (GAS ? 6 : 4) * ns + ns + 3 * n;
+  const long c = (static_cast<long>(k) * P.nj + j) * P.ni + i;
+  const long st[3] = {1, P.ni, static_cast<long>(P.ni) * P.nj};
+  const bool act[3] = {P.ie > P.is, P.je > P.js, P.ke > P.ks};
+  return derived_zone(
+      CURV, act, [&](int d, int a, int s) { return f.prim[v1 + d][c + s * st[a]]; },
+      [&](int a, int s) { return make_coords(P, b, k + (a == 2 ? s : 0), j + (a == 1 ? s : 0), i + (a == 0 ? s : 0)); });
+}
+template <bool GAS, class F>
+__device__ __forceinline__ void derived_components(const DerivedZone &z, int code, F &&f) {
+  if (code == (GAS ? ARTEMIS_VAR_GAS_DERIVED_DIVERGENCE : ARTEMIS_VAR_DUST_DERIVED_DIVERGENCE)) f(1, 0, z.div);
+  else if (code == (GAS ? ARTEMIS_VAR_GAS_DERIVED_VORTICITY : ARTEMIS_VAR_DUST_DERIVED_VORTICITY)) f(3, 0, z.w[0]), f(3, 1, z.w[1]), f(3, 2, z.w[2]);
+}
 template <int M>
 __device__ __forceinline__ double pair_lane(double v) { // v of lane ^ (1 << M), M <= 2
   const int lo = __double2loint(v), hi = __double2hiint(v);
@@ -100,6 +120,15 @@ struct Slots {
     return GAS ? g[c] : d[c];
   }
   static constexpr int width(int c) { return (c == 1 || (GAS ? c == 5 : c == 3)) ? 3 : 1; }
+  double q[NV];
+};
+// ... and the derived components of a species, a slot set of their own (the level kernel at S = 3 carries seven copies of
+// a set: four more slots in Slots<> would cost every existing instantiation about 56 VGPRs):  div | vorticity 1-3 | V
+template <bool GAS>
+struct DerivedSlots {
+  static constexpr int NV = 5, NCODE = 2, CODE0 = GAS ? ARTEMIS_VAR_GAS_DERIVED_DIVERGENCE : ARTEMIS_VAR_DUST_DERIVED_DIVERGENCE;
+  static constexpr int slot(int c) { return c == 0 ? 0 : 1; }
+  static constexpr int width(int c) { return c == 0 ? 1 : 3; }
   double q[NV];
 };
 template <int C>
@@ -135,6 +164,12 @@ __device__ __forceinline__ void level_leaf(const PackView &P, int b, int n, int 
     });
   }
   s.q[Slots<GAS>::NV - 1] = V;
+}
+template <bool CURV, bool GAS>
+__device__ __forceinline__ void level_leaf(const PackView &P, int b, int n, int k, int j, int i, DerivedSlots<GAS> &s) {
+  const DerivedZone z = load_derived<CURV, GAS>(P, b, n, k, j, i);
+  s.q[0] = z.vol * z.div, s.q[1] = z.vol * z.w[0], s.q[2] = z.vol * z.w[1], s.q[3] = z.vol * z.w[2];
+  s.q[4] = z.vol;
 }
 } // namespace
 } // namespace artemis

@@ -26,6 +26,9 @@ inline const char *field_var_text(int code) {
                                                        "gas.cons.density", "gas.cons.momentum", "gas.cons.total_energy",
                                                        "gas.cons.internal_energy", "dust.prim.density", "dust.prim.velocity",
                                                        "dust.cons.density", "dust.cons.momentum"};
+  static const char *const derived[ARTEMIS_VAR_DERIVED_END - ARTEMIS_VAR_DERIVED0] = {"gas.derived.divergence", "gas.derived.vorticity",
+                                                                                     "dust.derived.divergence", "dust.derived.vorticity"};
+  if (code >= ARTEMIS_VAR_DERIVED0 && code < ARTEMIS_VAR_DERIVED_END) return derived[code - ARTEMIS_VAR_DERIVED0];
   return (code >= 0 && code < ARTEMIS_VAR_COUNT) ? names[code] : "?";
 }
 
@@ -37,6 +40,8 @@ inline std::string field_unpack_plan(int nsel, const int *sel, int nsg, int nsd,
   for (int c = 0; c < ARTEMIS_VAR_COUNT; ++c) at[c] = -1;
   for (int e = 0; e < nsel; ++e) {
     const int code = sel[e];
+    if (code >= ARTEMIS_VAR_DERIVED0 && code < ARTEMIS_VAR_DERIVED_END)
+      return std::string("unpack fields: ") + field_var_text(code) + " is an output, not part of a state";
     if (code < 0 || code >= ARTEMIS_VAR_COUNT) return "unpack fields: unknown variable code " + std::to_string(code);
     if (at[code] >= 0) return std::string("unpack fields: ") + field_var_text(code) + " is given twice";
     const bool dust = code >= ARTEMIS_VAR_DUST_PRIM_DENSITY;

@@ -145,12 +145,30 @@ void launch_ml_floor_ghosts(const PackView &P, const int *blocks, int nblocks, h
 long history_workgroups(const PackView &P);
 void launch_history_sums(const PackView &P, double *sums, double *scratch, hipStream_t s);
 // kernels_fields.hip: the variables of artemis_hip_pack_fields as a kernel argument -- entry e holds variable code[e] and
-// its components start at component comp0[e] of a block's ncomp
-constexpr int FIELDS_MAX_SEL = 32;
+// its components start at component comp0[e] of a block's ncomp.  want_gas / want_dust: the fluids whose PLAIN codes
+// (0 .. 11) are named; the derived codes (16 .. 19) have a pass and launches of their own (field_passes below)
+constexpr int FIELDS_MAX_SEL = 32; // (two entries for each of the 16 variables; its size is part of every kernel's arguments)
 struct FieldSelection {
   int nsel, ncomp, want_gas, want_dust;
   int code[FIELDS_MAX_SEL], comp0[FIELDS_MAX_SEL];
 };
+// The two passes of a selection, for every launcher and for the ABI's checks: `plain` as the plain kernels take it, `derived`
+// the same entries with want_gas / want_dust naming the fluids whose DERIVED codes it holds; has_*: the pass has work
+struct FieldPasses {
+  FieldSelection plain, derived;
+  bool has_plain, has_derived;
+};
+inline FieldPasses field_passes(const FieldSelection &F) {
+  FieldPasses X;
+  X.plain = X.derived = F;
+  X.derived.want_gas = X.derived.want_dust = 0;
+  for (int e = 0; e < F.nsel; ++e) {
+    if (F.code[e] == ARTEMIS_VAR_GAS_DERIVED_DIVERGENCE || F.code[e] == ARTEMIS_VAR_GAS_DERIVED_VORTICITY) X.derived.want_gas = 1;
+    if (F.code[e] == ARTEMIS_VAR_DUST_DERIVED_DIVERGENCE || F.code[e] == ARTEMIS_VAR_DUST_DERIVED_VORTICITY) X.derived.want_dust = 1;
+  }
+  X.has_plain = F.want_gas || F.want_dust, X.has_derived = X.derived.want_gas || X.derived.want_dust;
+  return X;
+}
 void launch_pack_fields(const PackView &P, int block0, int nblocks, const FieldSelection &S, bool single, void *out, hipStream_t s);
 // ... at a chosen refinement level: block block0 + b is restricted shift[b] times (volume-weighted, shift > 0) or replicated
 // (shift < 0) and starts off[b] elements into `out`.  An extent of one zone is inactive: never halved or doubled.

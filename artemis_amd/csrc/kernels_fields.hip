@@ -12,6 +12,8 @@
 // two-zone lane would need a scalar path next to the vector one; the reads, always 8 bytes a lane, are two thirds of the
 // traffic of a float dump anyway.  A thread loads the primitives of one species once and forms every requested component
 // of that species from them; the selection is wave-uniform, so the switch below does not diverge.
+#include <type_traits>
+
 #include "device_math.hpp"
 #include "fields_device.hpp"
 #include "geometry.hpp"
@@ -52,7 +54,29 @@ __device__ __forceinline__ void put_zone(const PackView &P, const FieldSelection
   }
 }
 
+// ... and the derived components of the same selection (codes 16 .. 19: the stencil of fields_derived.hpp).  A pass of its
+// own in kernels of its own -- the DERIVED = true instantiations of the kernels below, launched only for a selection that names a
+// derived code -- so a request without one runs the kernels it always ran, and the plain kernels skip the derived codes.
 template <bool CURV, class OUT>
+__device__ __forceinline__ void put_zone_derived(const PackView &P, const FieldSelection &S, int b, int k, int j, int i, OUT *o, long zones) {
+  for (int n = 0; n < (S.want_gas ? P.gas.ns : 0); ++n) {
+    const DerivedZone z = load_derived<CURV, true>(P, b, n, k, j, i);
+    for (int e = 0; e < S.nsel; ++e) {
+      const long at = S.comp0[e] * zones;
+      derived_components<true>(z, S.code[e], [&](int w, int d, double v) { put(o, at + (w * n + d) * zones, v); });
+    }
+  }
+  for (int m = 0; m < (S.want_dust ? P.dust.ns : 0); ++m) {
+    const DerivedZone z = load_derived<CURV, false>(P, b, m, k, j, i);
+    for (int e = 0; e < S.nsel; ++e) {
+      const long at = S.comp0[e] * zones;
+      derived_components<false>(z, S.code[e], [&](int w, int d, double v) { put(o, at + (w * m + d) * zones, v); });
+    }
+  }
+}
+
+// (DERIVED: the derived pass -- S.want_gas / S.want_dust then say which fluids' DERIVED codes the selection names)
+template <bool CURV, class OUT, bool DERIVED = false>
 __global__ __launch_bounds__(FTX *FTY) void pack_fields_kernel(const PackView P, const FieldTiles T, const FieldSelection S,
                                                               int block0, OUT *out) {
   const int nx1 = P.ie - P.is + 1, nx2 = P.je - P.js + 1;
@@ -66,7 +90,8 @@ __global__ __launch_bounds__(FTX *FTY) void pack_fields_kernel(const PackView P,
     const int k = P.ks + static_cast<int>(bz % T.nkr);
     if (i > P.ie || j > P.je) continue;
     const long z = (static_cast<long>(k - P.ks) * nx2 + (j - P.js)) * nx1 + (i - P.is);
-    put_zone<CURV>(P, S, b, k, j, i, out + static_cast<long>(lb) * S.ncomp * zones + z, zones);
+    if constexpr (DERIVED) put_zone_derived<CURV>(P, S, b, k, j, i, out + static_cast<long>(lb) * S.ncomp * zones + z, zones);
+    else put_zone<CURV>(P, S, b, k, j, i, out + static_cast<long>(lb) * S.ncomp * zones + z, zones);
   }
 }
 
@@ -105,10 +130,10 @@ struct LevelTiles {
 };
 static_assert(sizeof(PackView) + sizeof(FieldSelection) + sizeof(LevelBlocks) + sizeof(LevelTiles) + 64 <= 4096, "kernel arguments");
 
-template <bool CURV, bool GAS, int S, class OUT>
+// (SL: the slot set that goes up the tree -- Slots<GAS>, or DerivedSlots<GAS> in the derived pass)
+template <bool CURV, bool GAS, int S, class SL, class OUT>
 __device__ __forceinline__ void level_species(const PackView &P, const FieldSelection &F, int b, int n, int k0, int j0, int i,
                                               bool store, OUT *o, long ozones) {
-  using SL = Slots<GAS>;
   const bool ia = P.ie > P.is, ja = P.je > P.js, ka = P.ke > P.ks;
   const int nbits = (ja ? 1 : 0) + (ka ? 1 : 0), jbit = 0, kbit = ja ? 1 : 0;
   SL v, sj[S], sk[S];
@@ -159,7 +184,7 @@ __device__ __forceinline__ void level_species(const PackView &P, const FieldSele
   }
 }
 
-template <bool CURV, class OUT, int S>
+template <bool CURV, class OUT, int S, bool DERIVED = false>
 __global__ __launch_bounds__(FTX *FTY) void pack_fields_level_kernel(const PackView P, const LevelTiles T, const FieldSelection F,
                                                                     const LevelBlocks B, int block0, OUT *out) {
   const bool ia = P.ie > P.is, ja = P.je > P.js, ka = P.ke > P.ks;
@@ -176,12 +201,14 @@ __global__ __launch_bounds__(FTX *FTY) void pack_fields_level_kernel(const PackV
     const int io = ia ? (ic - P.is) >> S : ic - P.is;
     const bool store = i <= P.ie && (!ia || ((i - P.is) & ((1 << S) - 1)) == 0);
     OUT *o = out + B.off[q] + (static_cast<long>(K) * T.nyo + J) * T.nxo + io;
-    for (int n = 0; n < (F.want_gas ? P.gas.ns : 0); ++n) level_species<CURV, true, S>(P, F, b, n, k0, j0, ic, store, o, ozones);
-    for (int m = 0; m < (F.want_dust ? P.dust.ns : 0); ++m) level_species<CURV, false, S>(P, F, b, m, k0, j0, ic, store, o, ozones);
+    using SG = std::conditional_t<DERIVED, DerivedSlots<true>, Slots<true>>;
+    using SD = std::conditional_t<DERIVED, DerivedSlots<false>, Slots<false>>;
+    for (int n = 0; n < (F.want_gas ? P.gas.ns : 0); ++n) level_species<CURV, true, S, SG>(P, F, b, n, k0, j0, ic, store, o, ozones);
+    for (int m = 0; m < (F.want_dust ? P.dust.ns : 0); ++m) level_species<CURV, false, S, SD>(P, F, b, m, k0, j0, ic, store, o, ozones);
   }
 }
 
-template <bool CURV, class OUT>
+template <bool CURV, class OUT, bool DERIVED = false>
 __global__ __launch_bounds__(FTX *FTY) void pack_fields_replicate_kernel(const PackView P, const LevelTiles T, const FieldSelection F,
                                                                         const LevelBlocks B, int block0, int r, OUT *out) {
   const int ri = P.ie > P.is ? r : 0, rj = P.je > P.js ? r : 0, rk = P.ke > P.ks ? r : 0;
@@ -192,8 +219,12 @@ __global__ __launch_bounds__(FTX *FTY) void pack_fields_replicate_kernel(const P
     const long bz = tile / (static_cast<long>(T.gx) * T.gy);
     const int q = static_cast<int>(bz / T.nzo), ko = static_cast<int>(bz % T.nzo);
     if (io >= T.nxo || jo >= T.nyo) continue;
-    put_zone<CURV>(P, F, block0 + B.lb[q], P.ks + (ko >> rk), P.js + (jo >> rj), P.is + (io >> ri),
-                   out + B.off[q] + (static_cast<long>(ko) * T.nyo + jo) * T.nxo + io, ozones);
+    if constexpr (DERIVED)
+      put_zone_derived<CURV>(P, F, block0 + B.lb[q], P.ks + (ko >> rk), P.js + (jo >> rj), P.is + (io >> ri),
+                             out + B.off[q] + (static_cast<long>(ko) * T.nyo + jo) * T.nxo + io, ozones);
+    else
+      put_zone<CURV>(P, F, block0 + B.lb[q], P.ks + (ko >> rk), P.js + (jo >> rj), P.is + (io >> ri),
+                     out + B.off[q] + (static_cast<long>(ko) * T.nyo + jo) * T.nxo + io, ozones);
   }
 }
 // The inverse (artemis_hip_unpack_fields): the same buffer read, the primitives of the interior zones written.  The
@@ -304,7 +335,7 @@ void launch_unpack_fields(const PackView &P, int block0, int nblocks, const Fiel
 
 namespace {
 template <bool CURV, class OUT>
-void launch_level_chunk(const PackView &P, int block0, const FieldSelection &F, const LevelBlocks &B, int shift, OUT *o, hipStream_t s) {
+void launch_level_chunk(const PackView &P, int block0, const FieldPasses &X, const LevelBlocks &B, int shift, OUT *o, hipStream_t s) {
   const int nx1 = P.ie - P.is + 1, nx2 = P.je - P.js + 1, nx3 = P.ke - P.ks + 1;
   LevelTiles T;
   T.nxo = level_extent(nx1, shift), T.nyo = level_extent(nx2, shift), T.nzo = level_extent(nx3, shift);
@@ -312,10 +343,20 @@ void launch_level_chunk(const PackView &P, int block0, const FieldSelection &F, 
   T.ntile = static_cast<long>(T.gx) * T.gy * T.nzo * B.n;
   if (T.ntile == 0) return;
   const dim3 t(FTX, FTY), g(static_cast<unsigned>(grid_capped(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG)));
-  if (shift == 1) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, B, block0, o);
-  else if (shift == 2) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, B, block0, o);
-  else if (shift == 3) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 3>), g, t, 0, s, P, T, F, B, block0, o);
-  else hipLaunchKernelGGL((pack_fields_replicate_kernel<CURV, OUT>), g, t, 0, s, P, T, F, B, block0, -shift, o);
+  if (X.has_plain) {
+    const FieldSelection &F = X.plain;
+    if (shift == 1) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, B, block0, o);
+    else if (shift == 2) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, B, block0, o);
+    else if (shift == 3) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 3>), g, t, 0, s, P, T, F, B, block0, o);
+    else hipLaunchKernelGGL((pack_fields_replicate_kernel<CURV, OUT>), g, t, 0, s, P, T, F, B, block0, -shift, o);
+  }
+  if (X.has_derived) {
+    const FieldSelection &F = X.derived;
+    if (shift == 1) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 1, true>), g, t, 0, s, P, T, F, B, block0, o);
+    else if (shift == 2) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 2, true>), g, t, 0, s, P, T, F, B, block0, o);
+    else if (shift == 3) hipLaunchKernelGGL((pack_fields_level_kernel<CURV, OUT, 3, true>), g, t, 0, s, P, T, F, B, block0, o);
+    else hipLaunchKernelGGL((pack_fields_replicate_kernel<CURV, OUT, true>), g, t, 0, s, P, T, F, B, block0, -shift, o);
+  }
 }
 } // namespace
 
@@ -325,6 +366,7 @@ void launch_pack_fields_level(const PackView &P, int block0, int nblocks, const 
                               const long *off, void *out, hipStream_t s) {
   if (F.ncomp == 0) return;
   const bool curv = P.coords != ARTEMIS_CARTESIAN;
+  const FieldPasses X = field_passes(F);
   for (int sh = -FIELDS_MAX_SHIFT; sh <= FIELDS_MAX_SHIFT; ++sh) {
     LevelBlocks B;
     B.n = 0;
@@ -333,12 +375,12 @@ void launch_pack_fields_level(const PackView &P, int block0, int nblocks, const 
       if (B.n == LEVEL_MAX_BLOCKS || (b == nblocks && B.n > 0)) {
         if (single) {
           float *o = static_cast<float *>(out);
-          if (curv) launch_level_chunk<true>(P, block0, F, B, sh, o, s);
-          else launch_level_chunk<false>(P, block0, F, B, sh, o, s);
+          if (curv) launch_level_chunk<true>(P, block0, X, B, sh, o, s);
+          else launch_level_chunk<false>(P, block0, X, B, sh, o, s);
         } else {
           double *o = static_cast<double *>(out);
-          if (curv) launch_level_chunk<true>(P, block0, F, B, sh, o, s);
-          else launch_level_chunk<false>(P, block0, F, B, sh, o, s);
+          if (curv) launch_level_chunk<true>(P, block0, X, B, sh, o, s);
+          else launch_level_chunk<false>(P, block0, X, B, sh, o, s);
         }
         B.n = 0;
       }
@@ -353,14 +395,27 @@ void launch_pack_fields(const PackView &P, int block0, int nblocks, const FieldS
   if (T.ntile == 0 || S.ncomp == 0) return;
   const dim3 t(FTX, FTY), g(static_cast<unsigned>(grid_capped(T.ntile < FIELDS_MAX_WG ? T.ntile : FIELDS_MAX_WG)));
   const bool curv = P.coords != ARTEMIS_CARTESIAN;
+  const FieldPasses X = field_passes(S);
   if (single) {
     float *o = static_cast<float *>(out);
-    if (curv) hipLaunchKernelGGL((pack_fields_kernel<true, float>), g, t, 0, s, P, T, S, block0, o);
-    else hipLaunchKernelGGL((pack_fields_kernel<false, float>), g, t, 0, s, P, T, S, block0, o);
+    if (X.has_plain) {
+      if (curv) hipLaunchKernelGGL((pack_fields_kernel<true, float>), g, t, 0, s, P, T, X.plain, block0, o);
+      else hipLaunchKernelGGL((pack_fields_kernel<false, float>), g, t, 0, s, P, T, X.plain, block0, o);
+    }
+    if (X.has_derived) {
+      if (curv) hipLaunchKernelGGL((pack_fields_kernel<true, float, true>), g, t, 0, s, P, T, X.derived, block0, o);
+      else hipLaunchKernelGGL((pack_fields_kernel<false, float, true>), g, t, 0, s, P, T, X.derived, block0, o);
+    }
   } else {
     double *o = static_cast<double *>(out);
-    if (curv) hipLaunchKernelGGL((pack_fields_kernel<true, double>), g, t, 0, s, P, T, S, block0, o);
-    else hipLaunchKernelGGL((pack_fields_kernel<false, double>), g, t, 0, s, P, T, S, block0, o);
+    if (X.has_plain) {
+      if (curv) hipLaunchKernelGGL((pack_fields_kernel<true, double>), g, t, 0, s, P, T, X.plain, block0, o);
+      else hipLaunchKernelGGL((pack_fields_kernel<false, double>), g, t, 0, s, P, T, X.plain, block0, o);
+    }
+    if (X.has_derived) {
+      if (curv) hipLaunchKernelGGL((pack_fields_kernel<true, double, true>), g, t, 0, s, P, T, X.derived, block0, o);
+      else hipLaunchKernelGGL((pack_fields_kernel<false, double, true>), g, t, 0, s, P, T, X.derived, block0, o);
+    }
   }
 }
 

@@ -20,6 +20,8 @@
 // every index of the directions still to come: a radial profile of a 256 x 128^2 block is 128 x 128 waves on the rows,
 // then 128 chains of 128, then one of 128 -- never one wave walking a block.
 // No LDS, no atomics, no tickets: no sum's order depends on the launch.  64-bit offsets.
+#include <type_traits>
+
 #include "device_math.hpp"
 #include "fields_device.hpp"
 #include "geometry.hpp"
@@ -63,9 +65,9 @@ __device__ __forceinline__ double chunk_sum(double v) {
 
 // The first pass for one species: DIR = 0 the x1 row of (k, j) in chunks, DIR = 1 the x2 column of (k, i), DIR = 2 the x3
 // column of (j, i); `a` and `c` are the two fixed indices in (k, j, i) order.
-template <bool CURV, bool GAS, int DIR>
-__device__ __forceinline__ void first_pass(const PackView &P, int b, int n, int a, int c, unsigned mask, Slots<GAS> &acc) {
-  using SL = Slots<GAS>;
+// (SL: Slots<GAS>, or DerivedSlots<GAS> in the derived pass)
+template <bool CURV, bool GAS, int DIR, class SL>
+__device__ __forceinline__ void first_pass(const PackView &P, int b, int n, int a, int c, unsigned mask, SL &acc) {
   if constexpr (DIR == 0) {
     const int nx1 = P.ie - P.is + 1;
     for (int i0 = 0; i0 < nx1; i0 += RTX) { // (wave-uniform)
@@ -100,9 +102,8 @@ __device__ __forceinline__ void first_pass(const PackView &P, int b, int n, int 
   }
 }
 
-template <bool GAS, class OUT>
-__device__ __forceinline__ void store_species(const FieldSelection &F, int n, const Slots<GAS> &acc, OUT *o, long ozones) {
-  using SL = Slots<GAS>;
+template <class SL, class OUT>
+__device__ __forceinline__ void store_species(const FieldSelection &F, int n, const SL &acc, OUT *o, long ozones) {
   for (int e = 0; e < F.nsel; ++e) {
     const long at = F.comp0[e] * ozones;
     const int code = F.code[e] - SL::CODE0;
@@ -115,9 +116,13 @@ __device__ __forceinline__ void store_species(const FieldSelection &F, int n, co
   put(o, F.ncomp * ozones, acc.q[SL::NV - 1]); // W: the same bits from every species
 }
 
-template <bool CURV, class OUT, int DIR>
+// DERIVED: the derived pass, a launch of its own -- F.want_gas / F.want_dust name the fluids whose derived codes are asked
+// for, T.gmask / T.dmask are masks of DerivedSlots; W is the same sum from either pass
+template <bool CURV, class OUT, int DIR, bool DERIVED = false>
 __global__ __launch_bounds__(RTX *RTY) void reduce_fields_kernel(const PackView P, const ReduceTiles T, const FieldSelection F, int block0,
                                                                 OUT *out) {
+  using SG = std::conditional_t<DERIVED, DerivedSlots<true>, Slots<true>>;
+  using SD = std::conditional_t<DERIVED, DerivedSlots<false>, Slots<false>>;
   const long ozones = static_cast<long>(T.nxo) * T.nyo * T.nzo;
   for (long tile = blockIdx.x; tile < T.ntile; tile += gridDim.x) {
     const int tx = static_cast<int>(tile % T.gx), ty = static_cast<int>((tile / T.gx) % T.gy);
@@ -145,14 +150,14 @@ __global__ __launch_bounds__(RTX *RTY) void reduce_fields_kernel(const PackView 
     const int b = block0 + lb;
     OUT *o = out + static_cast<long>(lb) * (F.ncomp + 1) * ozones + z;
     for (int n = 0; n < (F.want_gas ? P.gas.ns : 0); ++n) {
-      Slots<true> acc{}; // (the slots outside the mask stay 0.0 and are never stored)
+      SG acc{}; // (the slots outside the mask stay 0.0 and are never stored)
       first_pass<CURV, true, DIR>(P, b, n, a, c, T.gmask, acc);
-      if (store) store_species<true>(F, n, acc, o, ozones);
+      if (store) store_species(F, n, acc, o, ozones);
     }
     for (int m = 0; m < (F.want_dust ? P.dust.ns : 0); ++m) {
-      Slots<false> acc{};
+      SD acc{};
       first_pass<CURV, false, DIR>(P, b, m, a, c, T.dmask, acc);
-      if (store) store_species<false>(F, m, acc, o, ozones);
+      if (store) store_species(F, m, acc, o, ozones);
     }
   }
 }
@@ -290,11 +295,21 @@ void launch_first(const PackView &P, int block0, int nblocks, const FieldSelecti
   T.gx = dir == 0 ? 1 : (nx1 + RTX - 1) / RTX;
   T.gy = ((dir == 1 ? nx3 : nx2) + RTY - 1) / RTY;
   T.ntile = static_cast<long>(T.gx) * T.gy * (dir == 0 ? nx3 : 1) * nblocks;
-  T.gmask = slot_mask<Slots<true>>(F), T.dmask = slot_mask<Slots<false>>(F);
   const dim3 t(RTX, RTY), g(static_cast<unsigned>(grid_capped(T.ntile < REDUCE_MAX_WG ? T.ntile : REDUCE_MAX_WG)));
-  if (dir == 0) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 0>), g, t, 0, s, P, T, F, block0, o);
-  else if (dir == 1) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, block0, o);
-  else hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, block0, o);
+  const FieldPasses X = field_passes(F);
+  if (X.has_plain) {
+    T.gmask = slot_mask<Slots<true>>(F), T.dmask = slot_mask<Slots<false>>(F);
+    if (dir == 0) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 0>), g, t, 0, s, P, T, F, block0, o);
+    else if (dir == 1) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 1>), g, t, 0, s, P, T, F, block0, o);
+    else hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 2>), g, t, 0, s, P, T, F, block0, o);
+  }
+  if (X.has_derived) { // a launch of its own, for a selection that names a derived code
+    const FieldSelection &D = X.derived;
+    T.gmask = slot_mask<DerivedSlots<true>>(F), T.dmask = slot_mask<DerivedSlots<false>>(F);
+    if (dir == 0) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 0, true>), g, t, 0, s, P, T, D, block0, o);
+    else if (dir == 1) hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 1, true>), g, t, 0, s, P, T, D, block0, o);
+    else hipLaunchKernelGGL((reduce_fields_kernel<CURV, OUT, 2, true>), g, t, 0, s, P, T, D, block0, o);
+  }
 }
 
 template <class OUT>

@@ -556,6 +556,9 @@ class Simulation:
         """The named variables ('gas.prim.density', 'gas.prim.velocity', 'gas.prim.pressure', ...: include/artemis_driver.h
         "field output") of this rank's blocks, interior zones only, as [nblocks_local, ncomp, nz, ny, nx] float64 (float32
         with single=True).  Formed from the primitives on the device; nothing is materialised and the run is not disturbed.
+        'gas.derived.divergence' (one component per species), 'gas.derived.vorticity' (three) and their 'dust.derived.*' forms
+        are the velocity divergence and curl, formed on the device from a zone and its face neighbours, ghost zones included:
+        right across block, rank and coarse-fine edges, and a component like any other in the modes below.
         level = an int: every block resampled on the device to the zone size of refinement level `level` (0 the root grid,
         negative coarser) -- finer blocks by the volume-weighted mean of the reference's restriction, coarser ones by
         replication -- and returned as a list, in local block order, of [ncomp, nz_b, ny_b, nx_b] views of one buffer.  Each

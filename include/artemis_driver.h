@@ -235,6 +235,13 @@ int artemis_sim_outputs_describe(const artemis_sim_t *sim, char *json_out, long 
  * (floors applied; the pressure is (gamma-1) rho sie, not the stored slot, which the one-kernel stages never write), formed
  * from the primitives on the device (artemis_hip_pack_fields): no conserved array is materialised and the run's bits do
  * not change.
+ * Derived variables, outputs only: gas.derived.divergence (one component per species), gas.derived.vorticity (three), and
+ * dust.derived.divergence | .vorticity -- the velocity divergence and the curl in the mesh's orthogonal coordinates, formed
+ * on the device from the stored velocities of a zone and its six face neighbours, ghost zones included (artemis_hip.h,
+ * "derived variables", has the definition; in a rotating frame it is the frame's vorticity).  A request that names one
+ * first fills the ghost zones a stage loop may have left for later; that writes ghost zones only and the run's bits do not
+ * change.  They pass through gather, write, `fld` blocks and the level / reduced forms below like any other component;
+ * artemis_sim_scatter_fields refuses them (".. is an output, not part of a state").
  *
  * gather: host_out receives [local block][component][nk][nj][ni] over the INTERIOR zones of this rank's blocks, the
  * components in the order of `names`, as double or (single != 0) float; returns the number of components.  host_out =

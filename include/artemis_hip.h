@@ -258,10 +258,14 @@ enum artemis_field_var { ARTEMIS_VAR_GAS_PRIM_DENSITY = 0, ARTEMIS_VAR_GAS_PRIM_
                          ARTEMIS_VAR_GAS_PRIM_SIE = 3, ARTEMIS_VAR_GAS_CONS_DENSITY = 4, ARTEMIS_VAR_GAS_CONS_MOMENTUM = 5,
                          ARTEMIS_VAR_GAS_CONS_TOTAL_ENERGY = 6, ARTEMIS_VAR_GAS_CONS_INTERNAL_ENERGY = 7,
                          ARTEMIS_VAR_DUST_PRIM_DENSITY = 8, ARTEMIS_VAR_DUST_PRIM_VELOCITY = 9, ARTEMIS_VAR_DUST_CONS_DENSITY = 10,
-                         ARTEMIS_VAR_DUST_CONS_MOMENTUM = 11, ARTEMIS_VAR_COUNT = 12 };
+                         ARTEMIS_VAR_DUST_CONS_MOMENTUM = 11, ARTEMIS_VAR_COUNT = 12,
+                         /* outputs only, a second range (12 .. 15 stay unknown codes): see "derived variables" below */
+                         ARTEMIS_VAR_DERIVED0 = 16, ARTEMIS_VAR_GAS_DERIVED_DIVERGENCE = 16, ARTEMIS_VAR_GAS_DERIVED_VORTICITY = 17,
+                         ARTEMIS_VAR_DUST_DERIVED_DIVERGENCE = 18, ARTEMIS_VAR_DUST_DERIVED_VORTICITY = 19, ARTEMIS_VAR_DERIVED_END = 20 };
 /* artemis_hip_pack_fields fills out_dev (DEVICE) with [block - block0][component][k][j][i] over the interior zones of
  * blocks [block0, block0 + nblocks), the components in the order of the nsel codes of `sel` (HOST array, at most 32
- * entries; a code may repeat), as double or -- single != 0 -- as float.  Every value is the double PrimToCons
+ * entries -- kept at 32 with the derived codes below, twice the 16 variables there are: the selection travels as a kernel
+ * argument whose size every field kernel shares; a code may repeat), as double or -- single != 0 -- as float.  Every value is the double PrimToCons
  * (fill_derived.cpp:212-276) would leave in that slot: dfloor / siefloor applied to rho and sie, P = max(0, (gamma-1) rho
  * sie), M_d = rho v_d h_d with the scale factors of the pack's coordinates, eint = rho sie, E = eint + rho v^2 / 2, in the
  * expressions and operation order of artemis_hip_prim_to_cons; the float form is that double rounded to nearest.  No
@@ -270,7 +274,32 @@ enum artemis_field_var { ARTEMIS_VAR_GAS_PRIM_DENSITY = 0, ARTEMIS_VAR_GAS_PRIM_
  * dust code on a pack without dust (or a gas code without gas), nblocks < 0 or a block range outside the pack return
  * ARTEMIS_HIP_EINVAL.  Asynchronous on `stream`.
  * artemis_hip_pack_fields_bytes: the bytes all p->nblocks blocks take (a range takes nblocks / p->nblocks of it); 0 for
- * arguments pack_fields would refuse. */
+ * arguments pack_fields would refuse.
+ *
+ * Derived variables (codes 16 .. 19; outputs only, artemis_hip_unpack_fields refuses them): gas.derived.divergence (1
+ * component a species), gas.derived.vorticity (3), dust.derived.divergence, dust.derived.vorticity.  They read the face
+ * neighbours of a zone, so the GHOST ZONES of the pack must be current: at a block edge the neighbour is the ghost value --
+ * what the neighbouring block, the prolongation / restriction of a coarse-fine boundary or the boundary condition left
+ * there, i.e. what the next stage's reconstruction would see.  Only face neighbours are read, never an edge or corner ghost.
+ * v_d(c) is the STORED primitive velocity component d of the species at zone c = (k, j, i) (not floored, no density in
+ * it), c +- e_d the neighbour along direction d, and a direction is ACTIVE if the block has more than one zone along it.
+ * The velocities are the run's: in a rotating frame this is the vorticity in that frame (no 2 Omega is added).  Nothing is
+ * fused and every `/` is the correctly rounded IEEE division.
+ *   divergence: Gauss's theorem on the zone, on every coordinate system.  With A_d^-, A_d^+ = Coords::GetFaceArea of the
+ *   lower / upper face of direction d and V = Coords::Volume of the zone itself,
+ *       F_d^+ = A_d^+ * (0.5 * (v_d(c) + v_d(c + e_d)))
+ *       F_d^- = A_d^- * (0.5 * (v_d(c - e_d) + v_d(c)))
+ *       T_d   = F_d^+ - F_d^-                  (the literal 0.0 for an inactive direction)
+ *       div   = ((T_1 + T_2) + T_3) / V
+ *   vorticity: the curl in orthogonal coordinates, with the volume-averaged scale factors h of GetScaleFactors (the ones
+ *   cons.momentum uses; h_1 = 1, on Cartesian packs all three are 1), g_d(c) = h_d(c) * v_d(c) and the cell centres xi
+ *   (x1v, x2v, x3v; on Cartesian packs the mid-points of the faces) -- h and xi of a neighbour are that neighbour's own,
+ *       D_a[g](c) = (g(c + e_a) - g(c - e_a)) / (xi_a(c + e_a) - xi_a(c - e_a))       (the literal 0.0 if a is inactive)
+ *       w_1 = (D_2[g_3] - D_3[g_2]) / (h_2 * h_3)
+ *       w_2 = (D_3[g_1] - D_1[g_3]) / h_3
+ *       w_3 = (D_1[g_2] - D_2[g_1]) / h_2
+ * In the level and reduce entry points below a derived component is a component like any other: N = V q of it goes up the
+ * restriction tree or into the sums. */
 size_t artemis_hip_pack_fields_bytes(const artemis_pack_t *p, int nsel, const int *sel, int single);
 int artemis_hip_pack_fields(const artemis_pack_t *p, int block0, int nblocks, int nsel, const int *sel, int single,
                             void *out_dev, void *stream);
