@@ -39,7 +39,7 @@ CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-ffp-contract=off"] + NO_SI
 
 HIP_SOURCES = ["abi.hip", "kernels_unfused.hip", "kernels_fused.hip", "kernels_sources.hip", "kernels_stage_cell.hip",
                "kernels_diffusion.hip", "kernels_refine.hip", "kernels_amr.hip", "kernels_stage2d.hip", "kernels_curv.hip",
-               "kernels_ppm.hip", "kernels_history.hip", "kernels_fields.hip", "kernels_reduce.hip", "stage_plan.hip", "selftest.hip"]
+               "kernels_ppm.hip", "kernels_history.hip", "kernels_fields.hip", "kernels_reduce.hip", "kernels_sample.hip", "stage_plan.hip", "selftest.hip"]
 
 _INCLUDE_RE = re.compile(r'^\s*#\s*include\s*"([^"]+)"', re.M)
 _versions = {}

@@ -240,6 +240,10 @@ def load():
         "artemis_hip_reduce_fields_level_work_bytes": (C.c_size_t, [PPk, i, i, i, C.POINTER(i), i, i, C.POINTER(i)]),
         "artemis_hip_reduce_fields_level": (i, [PPk, i, i, i, C.POINTER(i), i, i, C.POINTER(i), vp, vp, vp]),
         "artemis_hip_unpack_fields": (i, [PPk, i, i, i, C.POINTER(i), i, vp, vp]),
+        "artemis_hip_locate_table_bytes": (C.c_size_t, [i, C.POINTER(d), C.POINTER(d), i]),
+        "artemis_hip_locate_table_build": (i, [i, C.POINTER(d), C.POINTER(d), i, vp, C.c_size_t]),
+        "artemis_hip_locate_points": (i, [PPk, vp, C.POINTER(d), C.c_long, vp, vp, vp]),
+        "artemis_hip_sample_fields": (i, [PPk, C.c_long, vp, vp, i, C.POINTER(i), i, vp, vp]),
         "artemis_hip_apply_bc": (i, [PPk, C.POINTER(i), C.POINTER(BcParams), vp]),
         "artemis_hip_external_gravity": (i, [PPk, C.POINTER(Gravity), d, d, vp]),
         "artemis_hip_rotating_frame_force": (i, [PPk, d, d, d, d, vp]),
@@ -362,6 +366,11 @@ EXPORTS_HIP = [
     "artemis_hip_halo_pack", "artemis_hip_halo_unpack", "artemis_hip_last_error",
     "artemis_hip_device_count", "artemis_hip_version", "artemis_hip_source_sha", "artemis_hip_object_sha",
 ]
+
+
+# ... and the point-sampling entry points, which include/artemis_hip_sample.h declares (a header of its own beside artemis_hip.h)
+EXPORTS_HIP_SAMPLE = ["artemis_hip_locate_table_bytes", "artemis_hip_locate_table_build", "artemis_hip_locate_points",
+                      "artemis_hip_sample_fields"]
 
 
 def source_sha():

@@ -13,10 +13,14 @@
 #include <unordered_map>
 
 #include "../../include/artemis_hip.h"
+#include "../../include/artemis_hip_sample.h"
 #include "../../include/artemis_rt.h"
+#include <cstdint>
 #include <vector>
 
 #include "kernels.hpp"
+#include "kernels_sample.hpp"
+#include "locate_table.hpp"
 #include "fields_shape.hpp"
 #include "options.hpp"
 #include "geometry_core.hpp"
@@ -414,6 +418,42 @@ int artemis_hip_unpack_fields(const artemis_pack_t *p, int block0, int nblocks, 
   if (!in_dev) return fail(ARTEMIS_HIP_EINVAL, "unpack fields: null in_dev");
   artemis::launch_unpack_fields(artemis::make_pack_view(*p), block0, nblocks, U, single != 0, in_dev, S(stream));
   return after_launch("unpack_fields");
+}
+
+// ---- point sampling (include/artemis_hip_sample.h) -----------------------------------------------------------------------
+size_t artemis_hip_locate_table_bytes(int nblocks, const double *bounds, const double *closed_hi, int active) {
+  return artemis_locate::table_bytes(nblocks, bounds, closed_hi, active);
+}
+int artemis_hip_locate_table_build(int nblocks, const double *bounds, const double *closed_hi, int active, void *table_host, size_t bytes) {
+  const char *bad = artemis_locate::table_build(nblocks, bounds, closed_hi, active, table_host, bytes);
+  return *bad ? fail(ARTEMIS_HIP_EINVAL, "%s", bad) : 0;
+}
+int artemis_hip_locate_points(const artemis_pack_t *p, const void *table_dev, const double *closed_hi, long npoints, const double *points_dev,
+                              int *loc_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  if (npoints < 0) return fail(ARTEMIS_HIP_EINVAL, "locate points: npoints = %ld", npoints);
+  if (npoints == 0) return 0;
+  if (!table_dev || !closed_hi || !points_dev || !loc_dev) return fail(ARTEMIS_HIP_EINVAL, "locate points: null table_dev, closed_hi, points_dev or loc_dev");
+  if (reinterpret_cast<uintptr_t>(loc_dev) % 16 || reinterpret_cast<uintptr_t>(table_dev) % 8)
+    return fail(ARTEMIS_HIP_EINVAL, "locate points: loc_dev is aligned to 16 bytes and table_dev to 8");
+  artemis::launch_locate_points(artemis::make_pack_view(*p), table_dev, closed_hi, npoints, points_dev, loc_dev, S(stream));
+  return after_launch("locate_points");
+}
+int artemis_hip_sample_fields(const artemis_pack_t *p, long npoints, const int *loc_dev, const long *order_dev, int nsel, const int *sel,
+                              int single, void *out_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldSelection F;
+  const char *bad = field_selection(p, nsel, sel, F);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (npoints < 0) return fail(ARTEMIS_HIP_EINVAL, "sample fields: npoints = %ld", npoints);
+  const artemis::FieldPasses X = artemis::field_passes(F);
+  if (((X.plain.want_gas || X.derived.want_gas) && !p->gas.prim) || ((X.plain.want_dust || X.derived.want_dust) && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "sample fields: the primitive tables of the fluids asked for are required");
+  if (npoints == 0 || F.ncomp == 0) return 0;
+  if (!loc_dev || !out_dev) return fail(ARTEMIS_HIP_EINVAL, "sample fields: null loc_dev or out_dev");
+  if (reinterpret_cast<uintptr_t>(loc_dev) % 16) return fail(ARTEMIS_HIP_EINVAL, "sample fields: loc_dev is aligned to 16 bytes");
+  artemis::launch_sample_fields(artemis::make_pack_view(*p), npoints, loc_dev, order_dev, F, single != 0, out_dev, S(stream));
+  return after_launch("sample_fields");
 }
 
 int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, double *dt_out,

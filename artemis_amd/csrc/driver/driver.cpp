@@ -35,6 +35,7 @@
 #include "checkpoint_hooks.hpp"
 #include "fields_host.hpp"
 #include "outputs_hooks.hpp"
+#include "sample_hooks.hpp"
 
 // The device kernel of the history integrals is referenced weakly: a host that exports the driver's C ABI without it (the
 // CPU stand-in of the tests) sums on the host instead.
@@ -190,6 +191,9 @@ enum { PG_BLAST, PG_LINWAVE, PG_ADVECTION, PG_CONSTANT, PG_STRAT, PG_BUMP, PG_CO
 } // namespace
 
 struct artemis_sim_impl {
+  // identity of this block list: every state built (a remesh and a restore build a new one) takes the next number, so a
+  // sample plan (sample.cpp) sees that the blocks it was located on are gone
+  long mesh_epoch = 0;
   artemis_host::ParameterInput pin;
   artemis_comm_t comm;
   bool has_comm = false;
@@ -3983,6 +3987,8 @@ struct artemis_sim {
   // the deck's <parthenon/output*> blocks once artemis_sim_enable_outputs or _outputs_describe has parsed them
   // (outputs.cpp; it survives the remeshes of an adaptive run, which replace `p`)
   artemis_out::State *outputs = nullptr;
+  // the sample plans of the handle (sample.cpp; they too survive the remeshes and locate again on the new blocks)
+  artemis_sample::State *samples = nullptr;
 };
 
 // A fresh state for the same deck on a given set of leaves (the problem generator runs on it: tables, `ic` states
@@ -3990,6 +3996,8 @@ struct artemis_sim {
 static std::unique_ptr<artemis_sim_impl> build_state(const artemis_sim &h, const std::vector<artemis_host::Leaf> *leaves,
                                                      bool adopting = false) {
   std::unique_ptr<artemis_sim_impl> np(new artemis_sim_impl());
+  static long epochs = 0;
+  np->mesh_epoch = ++epochs;
   if (leaves) np->forced_leaves = *leaves, np->have_forced = true;
   np->adopting = adopting;
   if (adopting && h.p) {
@@ -4328,6 +4336,40 @@ FieldsLayout fields_layout(artemis_sim_t *sim) {
 
 } // namespace artemis_out
 
+// What sample.cpp reaches of the handle (sample_hooks.hpp)
+namespace artemis_sample {
+
+State *&state_of(artemis_sim_t *sim) { return sim->samples; }
+long epoch_of(const artemis_sim_t *sim) { return sim->p->mesh_epoch; }
+Mesh mesh_of(const artemis_sim_t *sim) {
+  const artemis_sim_impl &S = *sim->p;
+  Mesh m;
+  m.epoch = S.mesh_epoch, m.nb = S.nb, m.ng = S.ng;
+  m.ns_gas = S.do_gas ? S.ns_gas : 0, m.ns_dust = S.do_dust ? S.ns_dust : 0;
+  for (int d = 0; d < 3; ++d) {
+    m.nx[d] = S.mbnx[d], m.closed_hi[d] = S.xmax[d];
+    if (S.mbnx[d] > 1) m.active |= 1 << d;
+  }
+  m.bounds.resize(static_cast<size_t>(6) * S.nb);
+  for (int b = 0; b < S.nb; ++b)
+    for (int d = 0; d < 3; ++d) m.bounds[6 * b + 2 * d] = S.blocks[b].xmin[d], m.bounds[6 * b + 2 * d + 1] = S.blocks[b].xmax[d];
+  m.geom = S.hgeom;
+  return m;
+}
+artemis_pack_t pack_of(const artemis_sim_t *sim) { return sim->p->make_pack(sim->p->base); }
+void *stream_of(const artemis_sim_t *sim) { return sim->p->stream; }
+void *stage_of(artemis_sim_t *sim, size_t bytes) {
+  const size_t need = (bytes + sizeof(double) - 1) / sizeof(double);
+  if (sim->p->field_stage.n < need) sim->p->field_stage.alloc(need);
+  return sim->p->field_stage.p;
+}
+void fill_stale_ghosts(artemis_sim_t *sim) { sim->p->fill_stale_ghosts(); }
+void host_components(artemis_sim_t *sim, int b, const std::vector<int> &codes, const std::vector<int> &comp0, int ncomp, std::vector<double> &vals) {
+  sim->p->host_block_components(b, codes, comp0, ncomp, vals, nullptr);
+}
+
+} // namespace artemis_sample
+
 extern "C" {
 
 const char *artemis_sim_last_error(void) { return g_sim_err.c_str(); }
@@ -4370,6 +4412,7 @@ void artemis_sim_destroy(artemis_sim_t *sim) {
   artemis_rt_device_sync();
   release_impl(sim->p);
   artemis_out::destroy(sim->outputs);
+  artemis_sample::destroy(sim->samples);
   delete sim;
 }
 long artemis_sim_evolve(artemis_sim_t *sim, long max_cycles) {

@@ -269,7 +269,80 @@ def _declare(L):
     L.artemis_sim_write_fields_reduced_level.argtypes = [vp, C.c_char_p, i, C.POINTER(C.c_char_p), i, i, i]
     L.artemis_sim_scatter_fields.restype = l
     L.artemis_sim_scatter_fields.argtypes = [vp, i, C.POINTER(C.c_char_p), i, vp, d]
+    L.artemis_sim_sample_plan_create.restype = l
+    L.artemis_sim_sample_plan_create.argtypes = [vp, l, vp]
+    L.artemis_sim_sample_plan_locations.argtypes = [vp, l, vp]
+    L.artemis_sim_sample_plan_values.restype = l
+    L.artemis_sim_sample_plan_values.argtypes = [vp, l, i, C.POINTER(C.c_char_p), i, vp]
+    L.artemis_sim_sample_plan_destroy.argtypes = [vp, l]
     L._sim_declared = True
+
+
+class SamplePlan:
+    """A list of points of a Simulation, located in this rank's blocks on the device (Simulation.sample_plan makes one; it
+    belongs to the simulation and is freed with it, or by close()).  After a remesh -- evolve() on an adaptive mesh,
+    force_refine() -- the next use locates the points again by itself."""
+
+    def __init__(self, sim, points):
+        if not isinstance(points, np.ndarray) or points.dtype != np.dtype(np.float64):
+            raise ValueError("sample points are a numpy array of float64, not %s"
+                             % (points.dtype if isinstance(points, np.ndarray) else type(points).__name__))
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError("sample points are [npoints, 3] (x1, x2, x3), not %s" % (tuple(points.shape),))
+        if not points.flags["C_CONTIGUOUS"]:
+            raise ValueError("sample points are a C-contiguous array")
+        self.sim, self.npoints = sim, int(points.shape[0])
+        self.id = sim.L.artemis_sim_sample_plan_create(sim.h, self.npoints, points.ctypes.data)
+        if self.id < 0:
+            self.id = None
+            raise RuntimeError(sim.L.artemis_sim_last_error().decode())
+
+    def _live(self):
+        if self.id is None or not getattr(self.sim, "h", None):
+            raise RuntimeError("the sample plan is closed")
+
+    def _locations(self):
+        self._live()
+        loc = np.empty((self.npoints, 4), dtype=np.int32)
+        if self.sim.L.artemis_sim_sample_plan_locations(self.sim.h, self.id, loc.ctypes.data):
+            raise RuntimeError(self.sim.L.artemis_sim_last_error().decode())
+        return loc
+
+    @property
+    def block(self):
+        """[npoints] int32: the local block that holds each point, -1 for a point that is not found (outside the mesh, not
+        finite, or in a block of another rank)"""
+        return np.ascontiguousarray(self._locations()[:, 0])
+
+    @property
+    def zone(self):
+        """[npoints, 3] int32: the zone of that block as k, j, i, interior-relative (gather's array indices); -1 where not found"""
+        return np.ascontiguousarray(self._locations()[:, 1:4])
+
+    def values(self, variables, single=False):
+        """The named variables (as gather names and orders them, the derived ones included) at the points: [ncomp, npoints]
+        float64 (float32 with single=True) in the order of the points, each value the one gather returns for the zone that
+        holds the point, bit for bit -- nothing is interpolated -- and NaN where the point is not found.  Formed from the
+        primitives on the device; the run is not disturbed.  RuntimeError for what the driver refuses (an unknown variable,
+        one of a fluid the run lacks, a closed plan)."""
+        self._live()
+        names, n = Simulation._names(variables)
+        L, h = self.sim.L, self.sim.h
+        nbytes = L.artemis_sim_sample_plan_values(h, self.id, n, names, int(single), None)
+        if nbytes < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        count = nbytes // (4 if single else 8)
+        out = np.empty(max(count, 1), dtype=np.float32 if single else np.float64)  # (never empty: NULL asks for the size)
+        ncomp = L.artemis_sim_sample_plan_values(h, self.id, n, names, int(single), out.ctypes.data)
+        if ncomp < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        return out[:count].reshape(ncomp, self.npoints)
+
+    def close(self):
+        """Free the plan (its device arrays); every later use raises RuntimeError."""
+        if self.id is not None and getattr(self.sim, "h", None):
+            self.sim.L.artemis_sim_sample_plan_destroy(self.sim.h, self.id)
+        self.id = None
 
 
 class Simulation:
@@ -637,6 +710,25 @@ class Simulation:
         t = float("nan") if time is None else float(time)
         if self.L.artemis_sim_scatter_fields(self.h, n, names, int(single), array.ctypes.data, t) < 0:
             raise RuntimeError(self.L.artemis_sim_last_error().decode())
+
+    def sample_plan(self, points):
+        """A SamplePlan of `points`, [npoints, 3] float64, C-contiguous, in the mesh's own coordinates (x1, x2, x3): each point
+        is found on the device in this rank's blocks -- leaves are half-open, the mesh's upper edge is closed, coordinates
+        along a direction with one zone are ignored, nothing wraps periodically -- and plan.values(variables) returns the
+        zone's values as gather forms them.  The cost follows the points, not the mesh: the midplane of a 256^3 block is a
+        256^2 plan (artemis_amd.sample.lattice), a zoom at the finest level of a refined mesh a lattice of that zone size,
+        an image of a disk artemis_amd.sample.from_cartesian of its pixels.  Not collective: a rank answers for its own blocks
+        (plan.block is -1 and the values NaN for the rest), and an in-domain point is found on exactly one rank.  ValueError
+        for an array of another dtype, shape or layout."""
+        return SamplePlan(self, points)
+
+    def sample(self, variables, points, single=False):
+        """(values [ncomp, npoints], block [npoints]) of a plan made, used once and closed: sample_plan(points).values(...)"""
+        plan = self.sample_plan(points)
+        try:
+            return plan.values(variables, single), plan.block
+        finally:
+            plan.close()
 
     # the complete forms a dump may hold, in the order load_fields prefers them
     _GAS_FORMS = (("gas.prim.density", "gas.prim.velocity", "gas.prim.sie"),

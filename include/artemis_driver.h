@@ -340,6 +340,29 @@ int artemis_sim_write_fields_reduced_level(artemis_sim_t *sim, const char *path,
 long artemis_sim_scatter_fields(artemis_sim_t *sim, int nvar, const char *const *names, int single, const void *host_in,
                                 double time);
 
+/* ---- sampling at points: the same variables AT ARBITRARY POINTS of the mesh's own coordinates (x1, x2, x3) -- a slice, a zoom
+ * at the finest level, a ray, a pixel grid -- the one field output whose cost follows the number of points and not the mesh.
+ * A point is found in this rank's blocks (half-open leaves, the mesh's xmax closed; coordinates along directions with one
+ * zone are ignored; no periodic wrapping) and takes the value gather returns for the zone that holds it, bit for bit:
+ * nothing is interpolated.  artemis_hip_sample.h has the definition; the search and the values run on the device.
+ *
+ * plan_create: points_host is [npoints][3] doubles; the plan keeps the points, their locations and the points' order sorted
+ * by location on the device, and belongs to the handle.  Returns its id (>= 0), < 0 on error.  npoints = 0 is a plan.
+ * plan_locations: loc_host receives [npoints][4] ints {local block, k, j, i} (interior-relative zone indices), all -1 for a
+ * point that is not found -- outside the mesh, not finite, or in a block of another rank.
+ * plan_values: host_out receives [component][npoints] in the caller's point order, the components in the order of `names`
+ * as gather orders them, double or (single != 0) float, NaN for a point that is not found; returns the number of components.
+ * host_out = NULL: returns the bytes of that buffer.  The values go through the staging buffer of gather (FIELDS_STAGE_MB).
+ * A plan survives a remesh: it records the block list it was located on, and the next plan_locations or plan_values after
+ * the blocks have been rebuilt locates again by itself.  scatter leaves plans alone (the mesh stays).  Plans are not part
+ * of a checkpoint.  The calls are not collective: every rank answers for its own blocks, and since the leaves tile the mesh
+ * an in-domain point is found on exactly one rank.  Primitives are read; the run's bits do not change.
+ * plan_destroy frees the plan; every call on an id that does not exist is an error (artemis_sim_last_error()). */
+long artemis_sim_sample_plan_create(artemis_sim_t *sim, long npoints, const double *points_host);
+int artemis_sim_sample_plan_locations(artemis_sim_t *sim, long id, int *loc_host);
+long artemis_sim_sample_plan_values(artemis_sim_t *sim, long id, int nvar, const char *const *names, int single, void *host_out);
+int artemis_sim_sample_plan_destroy(artemis_sim_t *sim, long id);
+
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured
  * with HIP events on the compute stream. */
