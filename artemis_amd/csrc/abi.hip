@@ -455,6 +455,34 @@ int artemis_hip_sample_fields(const artemis_pack_t *p, long npoints, const int *
   artemis::launch_sample_fields(artemis::make_pack_view(*p), npoints, loc_dev, order_dev, F, single != 0, out_dev, S(stream));
   return after_launch("sample_fields");
 }
+int artemis_hip_record_tick(void *ctl_dev, void *head_dev, const double *tstate_dev, double time, double dt, long every, long capacity,
+                            void *stream) {
+  if (every < 1 || capacity < 1) return fail(ARTEMIS_HIP_EINVAL, "record tick: every = %ld, capacity = %ld (both are at least 1)", every, capacity);
+  if (!ctl_dev || !head_dev) return fail(ARTEMIS_HIP_EINVAL, "record tick: null ctl_dev or head_dev");
+  if (reinterpret_cast<uintptr_t>(ctl_dev) % 8 || reinterpret_cast<uintptr_t>(head_dev) % 8 || reinterpret_cast<uintptr_t>(tstate_dev) % 8)
+    return fail(ARTEMIS_HIP_EINVAL, "record tick: ctl_dev, head_dev and tstate_dev are aligned to 8 bytes");
+  artemis::launch_record_tick(ctl_dev, head_dev, tstate_dev, time, dt, every, capacity, S(stream));
+  return after_launch("record_tick");
+}
+int artemis_hip_record_samples(const artemis_pack_t *p, long npoints, const int *loc_dev, const long *order_dev, int nsel, const int *sel,
+                               int single, const void *ctl_dev, long capacity, void *rows_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  artemis::FieldSelection F;
+  const char *bad = field_selection(p, nsel, sel, F);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (npoints < 0) return fail(ARTEMIS_HIP_EINVAL, "record samples: npoints = %ld", npoints);
+  if (capacity < 1) return fail(ARTEMIS_HIP_EINVAL, "record samples: capacity = %ld", capacity);
+  const artemis::FieldPasses X = artemis::field_passes(F);
+  if (((X.plain.want_gas || X.derived.want_gas) && !p->gas.prim) || ((X.plain.want_dust || X.derived.want_dust) && !p->dust.prim))
+    return fail(ARTEMIS_HIP_EINVAL, "record samples: the primitive tables of the fluids asked for are required");
+  if (!ctl_dev || !rows_dev) return fail(ARTEMIS_HIP_EINVAL, "record samples: null ctl_dev or rows_dev");
+  if (reinterpret_cast<uintptr_t>(ctl_dev) % 8) return fail(ARTEMIS_HIP_EINVAL, "record samples: ctl_dev is aligned to 8 bytes");
+  if (npoints == 0 || F.ncomp == 0) return 0;
+  if (!loc_dev) return fail(ARTEMIS_HIP_EINVAL, "record samples: null loc_dev");
+  if (reinterpret_cast<uintptr_t>(loc_dev) % 16) return fail(ARTEMIS_HIP_EINVAL, "record samples: loc_dev is aligned to 16 bytes");
+  artemis::launch_record_samples(artemis::make_pack_view(*p), npoints, loc_dev, order_dev, F, single != 0, ctl_dev, capacity, rows_dev, S(stream));
+  return after_launch("record_samples");
+}
 
 int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, double *dt_out,
                             void *stream) {

@@ -35,6 +35,7 @@
 #include "checkpoint_hooks.hpp"
 #include "fields_host.hpp"
 #include "outputs_hooks.hpp"
+#include "record_hooks.hpp"
 #include "sample_hooks.hpp"
 
 // The device kernel of the history integrals is referenced weakly: a host that exports the driver's C ABI without it (the
@@ -3331,6 +3332,12 @@ long artemis_sim_impl::evolve(long max_cycles, artemis_sim_t *owner) {
   const bool outs = owner && artemis_out::enabled(artemis_out::state_of(owner));
   double deadline = outs ? artemis_out::deadline(artemis_out::state_of(owner)) : HUGE_VAL;
   bool leave = false;
+  // Recorders of the handle (artemis_sim_record_create): after every cycle the tick and the sample of each are queued behind
+  // the step -- inside the captured graph when there is one -- and the host only sees to it that no device buffer overflows.
+  const bool rec = owner && artemis_record::attached(artemis_record::state_of(owner));
+  auto record_room = [&]() { // before a cycle is queued
+    if (rec && artemis_record::room(owner) < 1) artemis_record::drain(owner);
+  };
   auto outputs_due = [&]() { // after the host's clock has moved
     if (!outs || time < deadline) return;
     leave = artemis_out::write_due(owner, true);
@@ -3370,9 +3377,11 @@ long artemis_sim_impl::evolve(long max_cycles, artemis_sim_t *owner) {
     CK(artemis_rt_stream_sync(stream), "sync");
     for (long m = 0; m < todo; ++m, ++n, ++plain_steps) {
       const int key = base;
+      record_room(); // (a batch ends where a recorder's buffer is full: the rows go to the host, the device clock stays)
       if (graph_ok && plain_steps >= 3 && gexec[key]) {
         base = gnext[key], cons_valid = false;
         CK(artemis_rt_graph_launch(gexec[key], stream), "graph launch");
+        if (rec) artemis_record::count_cycle(owner);
         ncycle++;
         continue;
       }
@@ -3382,6 +3391,7 @@ long artemis_sim_impl::evolve(long max_cycles, artemis_sim_t *owner) {
       if (multi && comm.allreduce_min_dev(comm.ctx, tstate.p + 2, stream))
         throw std::runtime_error("allreduce_min_dev failed");
       CK(artemis_hip_advance_dt(tstate.p, tlim, nstages, beta, stream), "advance_dt");
+      if (rec) artemis_record::record_cycle(owner, tstate.p, 0.0, 0.0); // (row index, cycle and clock are read on the device)
       if (capture) { // nothing has run yet: instantiate and launch what was recorded
         gexec[key] = artemis_rt_capture_end(stream);
         if (!gexec[key]) throw HipFail(std::string("graph capture failed: ") + artemis_hip_last_error());
@@ -3426,6 +3436,7 @@ long artemis_sim_impl::evolve(long max_cycles, artemis_sim_t *owner) {
       }
     }
     Real est;
+    record_room();
     if (use_fused) {
       step_fused(true, false);
       const bool dev_reduce = has_comm && (nranks > 1 || loopback) && comm.allreduce_min_dev;
@@ -3446,6 +3457,7 @@ long artemis_sim_impl::evolve(long max_cycles, artemis_sim_t *owner) {
     ndt = std::min(ndt, est);
     if (tlim > 0.0 && time < tlim && (tlim - time) < ndt) ndt = tlim - time;
     dt = ndt;
+    if (rec) artemis_record::record_cycle(owner, nullptr, time, dt);
     outputs_due();
   }
   for (void *g : gexec) artemis_rt_graph_destroy(g);
@@ -3989,6 +4001,8 @@ struct artemis_sim {
   artemis_out::State *outputs = nullptr;
   // the sample plans of the handle (sample.cpp; they too survive the remeshes and locate again on the new blocks)
   artemis_sample::State *samples = nullptr;
+  // the recorders of the handle (record.cpp): time series of a plan's sample, taken on the device inside the time loop
+  artemis_record::State *records = nullptr;
 };
 
 // A fresh state for the same deck on a given set of leaves (the problem generator runs on it: tables, `ic` states
@@ -4370,6 +4384,11 @@ void host_components(artemis_sim_t *sim, int b, const std::vector<int> &codes, c
 
 } // namespace artemis_sample
 
+// What record.cpp reaches of the handle (record_hooks.hpp; the rest goes through sample_hooks.hpp)
+namespace artemis_record {
+State *&state_of(artemis_sim_t *sim) { return sim->records; }
+} // namespace artemis_record
+
 extern "C" {
 
 const char *artemis_sim_last_error(void) { return g_sim_err.c_str(); }
@@ -4412,6 +4431,7 @@ void artemis_sim_destroy(artemis_sim_t *sim) {
   artemis_rt_device_sync();
   release_impl(sim->p);
   artemis_out::destroy(sim->outputs);
+  artemis_record::destroy(sim->records);
   artemis_sample::destroy(sim->samples);
   delete sim;
 }
@@ -4423,7 +4443,8 @@ long artemis_sim_evolve(artemis_sim_t *sim, long max_cycles) {
   }
   const bool amr = sim->p->adaptive && sim->p->refine_field;
   const bool outs = artemis_out::enabled(sim->outputs);
-  if (!amr && !outs) {
+  const bool rec = artemis_record::attached(sim->records);
+  if (!amr && !outs && !rec) {
     GUARD(n = sim->p->evolve(max_cycles), return -1)
     return n;
   }
@@ -4438,19 +4459,28 @@ long artemis_sim_evolve(artemis_sim_t *sim, long max_cycles) {
   auto run = [&]() {
     n = 0;
     double wall = 0.0;
+    if (rec) artemis_record::begin_evolve(sim, sim->p->ncycle);
     if (outs) {
       sim->p->ensure_first_dt();
       artemis_out::write_due(sim, false);
     }
     while (max_cycles < 0 || n < max_cycles) {
+      // (the adaptive call deliberately gets NO owner: its outputs and its recorders are served below, after the remesh
+      //  check of the cycle -- with an owner, evolve would record the cycle too and every row would appear twice)
       const long k = amr ? sim->p->evolve(1) : sim->p->evolve(max_cycles < 0 ? -1 : max_cycles - n, sim);
       wall += sim->p->last_wall;
       if (k <= 0) break;
       n += k;
       if (amr) remesh(*sim, false);
+      if (amr && rec) { // (the uniform loop records inside evolve; here a row follows the remesh check of its cycle)
+        if (artemis_record::room(sim) < 1) artemis_record::drain(sim);
+        artemis_record::record_cycle(sim, nullptr, sim->p->time, sim->p->dt);
+      }
       if (outs) {
         artemis_out::write_due(sim, false);
         if (ended()) break;
+      } else if (!amr) {
+        break; // (recorders alone: the loop has run to its end in one call)
       }
     }
     if (outs && ended()) artemis_out::write_final(sim);

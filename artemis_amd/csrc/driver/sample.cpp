@@ -32,6 +32,7 @@
 #include "../options.hpp"
 #include "checkpoint_hooks.hpp"
 #include "outputs_hooks.hpp"
+#include "record_hooks.hpp"
 #include "sample_hooks.hpp"
 
 extern "C" int artemis_hip_locate_points(const artemis_pack_t *p, const void *table_dev, const double *closed_hi, long npoints,
@@ -212,6 +213,23 @@ size_t values(artemis_sim_t *sim, Plan &P, const std::vector<int> &codes, bool s
 }
 
 } // namespace
+
+bool plan_exists(artemis_sim_t *sim, long id) {
+  State *st = state_of(sim);
+  return st && st->plans.count(id) != 0;
+}
+PlanView located_plan(artemis_sim_t *sim, long id) {
+  Plan &P = plan_of(sim, id);
+  ensure_located(sim, P);
+  PlanView v;
+  v.npoints = P.npoints;
+  v.loc_dev = static_cast<const int *>(P.loc_dev.p), v.order_dev = static_cast<const long *>(P.order_dev.p);
+  return v;
+}
+size_t plan_values(artemis_sim_t *sim, long id, const std::vector<int> &codes, bool single, void *host_out) {
+  return values(sim, plan_of(sim, id), codes, single, host_out);
+}
+
 } // namespace artemis_sample
 
 extern "C" {
@@ -295,6 +313,7 @@ int artemis_sim_sample_plan_destroy(artemis_sim_t *sim, long id) {
   try {
     if (!sim) throw std::runtime_error("sample_plan_destroy: no simulation");
     plan_of(sim, id);
+    if (artemis_record::plan_in_use(sim, id)) throw std::runtime_error("sample plan " + std::to_string(id) + " is in use by a recorder: close the recorder first");
     state_of(sim)->plans.erase(id);
     return 0;
   } catch (const std::exception &e) {

@@ -38,5 +38,16 @@ void host_components(artemis_sim_t *sim, int b, const std::vector<int> &codes, c
 
 // ---- sample.cpp ------------------------------------------------------------------------------------------------------
 void destroy(State *st);
+// what a recorder (record.cpp) uses of a plan: located on the current blocks first, if they changed.  The pointers stay
+// valid until the plan locates again or is destroyed; the device ones are NULL on a host without the kernels.
+struct PlanView {
+  long npoints = 0;
+  const int *loc_dev = nullptr;
+  const long *order_dev = nullptr;
+};
+bool plan_exists(artemis_sim_t *sim, long id);
+PlanView located_plan(artemis_sim_t *sim, long id);
+// [ncomp][npoints] of `codes` at the plan's points into host_out: artemis_sim_sample_plan_values without the names
+size_t plan_values(artemis_sim_t *sim, long id, const std::vector<int> &codes, bool single, void *host_out);
 
 } // namespace artemis_sample

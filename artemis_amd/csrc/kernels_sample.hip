@@ -156,4 +156,80 @@ void launch_sample_fields(const PackView &P, long npoints, const int *loc, const
   else launch_sample_passes(P, npoints, l, order, X, static_cast<double *>(out), s);
 }
 
+// ---- recording inside the time loop (artemis_hip_record_tick, artemis_hip_record_samples) -------------------------------------
+// What a replayed graph cannot take by value lives in the control block on the device: the tick (one thread) counts the cycle,
+// decides whether it is due and opens the row; the sample kernels read the row index there -- a load from a kernel-argument
+// address, the same for every lane: one scalar load per wave -- and are sample_fields_kernel otherwise, with the same
+// put_point / put_point_derived / put_missing, so a row holds the bits artemis_hip_sample_fields stores.  Only the tick
+// writes the control block; plain stores everywhere.
+namespace {
+__global__ __launch_bounds__(64) void record_tick_kernel(artemis_record_ctl_t *ctl, artemis_record_head_t *head, const double *tstate,
+                                                        double time, double dt, long every, long capacity) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long long seen = ++ctl->seen, cycle = ++ctl->cycle;
+  long long slot = -1;
+  if (seen % every == 0) {
+    if (ctl->rows < capacity) slot = ctl->rows++;
+    else ++ctl->dropped;
+  }
+  ctl->slot = slot;
+  if (slot >= 0) {
+    head[slot].cycle = cycle;
+    head[slot].time = tstate ? tstate[0] : time;
+    head[slot].dt = tstate ? tstate[1] : dt;
+  }
+}
+
+template <bool CURV, class OUT, bool DERIVED>
+__global__ __launch_bounds__(STX) void record_samples_kernel(const PackView P, const FieldSelection S, long npoints, const int4 *loc,
+                                                            const long *order, const artemis_record_ctl_t *__restrict__ ctl, long capacity,
+                                                            long row, OUT *rows) {
+  const long long slot = ctl->slot; // wave-uniform
+  if (slot < 0 || slot >= capacity) return;
+  OUT *out = rows + slot * row;
+  const int nx1 = P.ie - P.is + 1, nx2 = P.je - P.js + 1, nx3 = P.ke - P.ks + 1;
+  for (long t = static_cast<long>(blockIdx.x) * STX + threadIdx.x; t < npoints; t += static_cast<long>(gridDim.x) * STX) {
+    const long p = order ? order[t] : t;
+    if (p < 0 || p >= npoints) continue;
+    const int4 l = loc[p]; // {block, k, j, i}
+    OUT *o = out + p;
+    const bool found = l.x >= 0 && l.x < P.nb && l.y >= 0 && l.y < nx3 && l.z >= 0 && l.z < nx2 && l.w >= 0 && l.w < nx1;
+    if (!found) put_missing<DERIVED>(P, S, o, npoints);
+    else if constexpr (DERIVED) put_point_derived<CURV>(P, S, l.x, P.ks + l.y, P.js + l.z, P.is + l.w, o, npoints);
+    else put_point<CURV>(P, S, l.x, P.ks + l.y, P.js + l.z, P.is + l.w, o, npoints);
+  }
+}
+
+template <class OUT>
+void launch_record_passes(const PackView &P, long npoints, const int4 *loc, const long *order, const FieldPasses &X,
+                          const artemis_record_ctl_t *ctl, long capacity, long row, OUT *rows, hipStream_t s) {
+  const dim3 t(STX), g(sample_grid(npoints));
+  const bool curv = P.coords != ARTEMIS_CARTESIAN;
+  if (X.has_plain) {
+    if (curv) hipLaunchKernelGGL((record_samples_kernel<true, OUT, false>), g, t, 0, s, P, X.plain, npoints, loc, order, ctl, capacity, row, rows);
+    else hipLaunchKernelGGL((record_samples_kernel<false, OUT, false>), g, t, 0, s, P, X.plain, npoints, loc, order, ctl, capacity, row, rows);
+  }
+  if (X.has_derived) {
+    if (curv) hipLaunchKernelGGL((record_samples_kernel<true, OUT, true>), g, t, 0, s, P, X.derived, npoints, loc, order, ctl, capacity, row, rows);
+    else hipLaunchKernelGGL((record_samples_kernel<false, OUT, true>), g, t, 0, s, P, X.derived, npoints, loc, order, ctl, capacity, row, rows);
+  }
+}
+} // namespace
+
+void launch_record_tick(void *ctl, void *head, const double *tstate, double time, double dt, long every, long capacity, hipStream_t s) {
+  hipLaunchKernelGGL(record_tick_kernel, dim3(1), dim3(64), 0, s, static_cast<artemis_record_ctl_t *>(ctl),
+                     static_cast<artemis_record_head_t *>(head), tstate, time, dt, every, capacity);
+}
+
+void launch_record_samples(const PackView &P, long npoints, const int *loc, const long *order, const FieldSelection &S, bool single,
+                           const void *ctl, long capacity, void *rows, hipStream_t s) {
+  if (npoints <= 0 || S.ncomp == 0) return;
+  const FieldPasses X = field_passes(S);
+  const int4 *l = reinterpret_cast<const int4 *>(loc);
+  const artemis_record_ctl_t *c = static_cast<const artemis_record_ctl_t *>(ctl);
+  const long row = static_cast<long>(S.ncomp) * npoints;
+  if (single) launch_record_passes(P, npoints, l, order, X, c, capacity, row, static_cast<float *>(rows), s);
+  else launch_record_passes(P, npoints, l, order, X, c, capacity, row, static_cast<double *>(rows), s);
+}
+
 } // namespace artemis

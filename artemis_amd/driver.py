@@ -275,6 +275,13 @@ def _declare(L):
     L.artemis_sim_sample_plan_values.restype = l
     L.artemis_sim_sample_plan_values.argtypes = [vp, l, i, C.POINTER(C.c_char_p), i, vp]
     L.artemis_sim_sample_plan_destroy.argtypes = [vp, l]
+    L.artemis_sim_record_create.restype = l
+    L.artemis_sim_record_create.argtypes = [vp, l, i, C.POINTER(C.c_char_p), l, l, i]
+    L.artemis_sim_record_rows.restype = l
+    L.artemis_sim_record_rows.argtypes = [vp, l]
+    L.artemis_sim_record_read.restype = l
+    L.artemis_sim_record_read.argtypes = [vp, l, vp, vp, vp, vp, i]
+    L.artemis_sim_record_destroy.argtypes = [vp, l]
     L._sim_declared = True
 
 
@@ -342,6 +349,76 @@ class SamplePlan:
         """Free the plan (its device arrays); every later use raises RuntimeError."""
         if self.id is not None and getattr(self.sim, "h", None):
             self.sim.L.artemis_sim_sample_plan_destroy(self.sim.h, self.id)
+        self.id = None
+
+
+class TimeSeries:
+    """What Recorder.read returns: cycle [n] int64, time [n], dt [n] float64, values [n, ncomp, npoints]"""
+
+    def __init__(self, cycle, time, dt, values):
+        self.cycle, self.time, self.dt, self.values = cycle, time, dt, values
+
+
+# Rows a recorder's device buffers hold when the caller names no capacity: at most 4096 rows and at most 64 MiB.  A design
+# constant, not a measurement: large enough that a run drains rarely, small enough not to compete with the state for memory.
+RECORD_DEFAULT_ROWS, RECORD_DEFAULT_BYTES = 4096, 64 << 20
+
+
+class Recorder:
+    """A time series of a SamplePlan's values, recorded on the device inside evolve() (Simulation.record makes one; it
+    belongs to the simulation and is freed with it, or by close()).  After every `every`-th cycle completed since it was
+    made one row is appended: the cycle number, the time the values hold at, the next step's dt, and what
+    plan.values(variables, single) would return at that moment, bit for bit.  Rank-local like a plan, not part of a
+    checkpoint, nothing interpolated in space or time."""
+
+    def __init__(self, sim, plan, variables, every, capacity, single, owns_plan):
+        self.sim, self.plan, self.single, self._owns_plan, self.id = sim, plan, bool(single), owns_plan, None
+        self.variables = [variables] if isinstance(variables, str) else list(variables)
+        names, n = Simulation._names(self.variables)
+        L, h = sim.L, sim.h
+        if capacity is None:
+            row = L.artemis_sim_sample_plan_values(h, plan.id, n, names, int(self.single), None)  # bytes of [ncomp][npoints]
+            if row < 0:
+                raise RuntimeError(L.artemis_sim_last_error().decode())
+            capacity = max(1, min(RECORD_DEFAULT_ROWS, RECORD_DEFAULT_BYTES // max(row, 1)))
+        self.every, self.capacity = int(every), int(capacity)
+        rid = L.artemis_sim_record_create(h, plan.id, n, names, self.every, self.capacity, int(self.single))
+        if rid < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        self.id = rid
+        self.ncomp = L.artemis_sim_record_read(h, rid, None, None, None, None, 0)  # (no buffer: the size query)
+
+    def _live(self):
+        if self.id is None or not getattr(self.sim, "h", None):
+            raise RuntimeError("the recorder is closed")
+
+    @property
+    def rows(self):
+        """rows recorded so far and not cleared by read(clear=True); waits for the device and empties its buffers first"""
+        self._live()
+        n = self.sim.L.artemis_sim_record_rows(self.sim.h, self.id)
+        if n < 0:
+            raise RuntimeError(self.sim.L.artemis_sim_last_error().decode())
+        return n
+
+    def read(self, clear=False):
+        """A TimeSeries of the rows so far, oldest first; clear=True forgets them afterwards (the counters go on)."""
+        n = self.rows
+        L, h, ncomp = self.sim.L, self.sim.h, self.ncomp
+        cycle, time, dt = np.empty(n, dtype=np.int64), np.empty(n), np.empty(n)
+        count = n * ncomp * self.plan.npoints
+        values = np.empty(max(count, 1), dtype=np.float32 if self.single else np.float64)  # (never empty: NULL is "no buffer")
+        if L.artemis_sim_record_read(h, self.id, cycle.ctypes.data if n else None, time.ctypes.data if n else None,
+                                     dt.ctypes.data if n else None, values.ctypes.data, int(bool(clear))) < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        return TimeSeries(cycle, time, dt, values[:count].reshape(n, ncomp, self.plan.npoints))
+
+    def close(self):
+        """Free the recorder (and the plan it made for itself); every later use raises RuntimeError."""
+        if self.id is not None and getattr(self.sim, "h", None):
+            self.sim.L.artemis_sim_record_destroy(self.sim.h, self.id)
+            if self._owns_plan:
+                self.plan.close()
         self.id = None
 
 
@@ -729,6 +806,32 @@ class Simulation:
             return plan.values(variables, single), plan.block
         finally:
             plan.close()
+
+    def record(self, points_or_plan, variables, every=1, capacity=None, single=False):
+        """A Recorder: after every `every`-th cycle that evolve() completes from now on, one row {cycle, time, dt, values
+        [ncomp, npoints]} is taken ON THE DEVICE, inside the time loop and its captured graphs -- the cycle number, time and
+        next dt that ncycle / time / dt would show had evolve returned there, and what plan.values(variables, single) would
+        return at that moment, bit for bit.  points_or_plan: a SamplePlan of this simulation, or an [npoints, 3] float64 array
+        (a plan is made; the recorder owns and closes it).  capacity: rows the device buffers hold before evolve() copies
+        them to the host at a batch boundary (no row is lost); None: max(1, min(4096, 64 MiB // bytes of a row)).  The run is
+        not disturbed: the same bits with and without recorders.  Only evolve() records; scatter, load_fields, force_refine,
+        gather and values do not.  ValueError: every < 1, capacity < 1, a plan of another simulation; RuntimeError: what the
+        driver refuses (an unknown variable, a closed plan)."""
+        if int(every) < 1:
+            raise ValueError("every = %r: at least 1" % (every,))
+        if capacity is not None and int(capacity) < 1:
+            raise ValueError("capacity = %r: at least 1 row" % (capacity,))
+        if isinstance(points_or_plan, SamplePlan):
+            if points_or_plan.sim is not self:
+                raise ValueError("the sample plan belongs to another simulation")
+            points_or_plan._live()
+            return Recorder(self, points_or_plan, variables, every, capacity, single, False)
+        plan = self.sample_plan(points_or_plan)
+        try:
+            return Recorder(self, plan, variables, every, capacity, single, True)
+        except Exception:
+            plan.close()
+            raise
 
     # the complete forms a dump may hold, in the order load_fields prefers them
     _GAS_FORMS = (("gas.prim.density", "gas.prim.velocity", "gas.prim.sie"),

@@ -363,6 +363,28 @@ int artemis_sim_sample_plan_locations(artemis_sim_t *sim, long id, int *loc_host
 long artemis_sim_sample_plan_values(artemis_sim_t *sim, long id, int nvar, const char *const *names, int single, void *host_out);
 int artemis_sim_sample_plan_destroy(artemis_sim_t *sim, long id);
 
+/* ---- a time series of samples, recorded on the device inside the time loop.  A recorder has a plan of this handle, a
+ * selection of variables, `every` >= 1, a row `capacity` >= 1 and a precision.  `seen` counts the cycles artemis_sim_evolve
+ * has completed since the recorder was made; after a completed cycle with seen % every == 0 one row is appended:
+ *   cycle, time, dt   what artemis_sim_ncycle / _time / _dt would return had evolve returned after exactly that cycle
+ *   values            [ncomp][npoints]: what artemis_sim_sample_plan_values would return at that moment, bit for bit
+ * (on an adaptive mesh: after that cycle's remesh check, the plan located again when the blocks changed).  Only
+ * artemis_sim_evolve advances `seen`.  The record steps run inside the time loop and inside its captured graphs; rows
+ * collect on the device in buffers of `capacity` rows, which the loop empties into host storage at a batch boundary when they
+ * are full -- the only synchronisation a recorder adds -- so no row is lost.  The run is not disturbed: state, time, dt
+ * and cycle count are the same bits with and without recorders (a derived variable fills ghost zones first, as a gather does).
+ * A recorder is rank-local like its plan, is not part of a checkpoint, and lives until _destroy or the end of the handle.
+ *   _create   an id >= 0; -1: no such plan, an unknown variable, every < 1, capacity < 1, an allocation that failed
+ *   _rows     the rows recorded and not yet cleared (it drains the device buffers first); -1 on failure
+ *   _read     copies them, oldest first, into the buffers that are not NULL -- cycle_out [rows] (long), time_out and dt_out
+ *             [rows], values_out [rows][ncomp][npoints] (double, or float for a single recorder) -- and, with clear != 0,
+ *             forgets them; returns ncomp.  With every buffer NULL nothing is copied or cleared: ask _rows for the sizes.
+ * artemis_sim_sample_plan_destroy refuses a plan that a live recorder uses. */
+long artemis_sim_record_create(artemis_sim_t *sim, long plan_id, int nvar, const char *const *names, long every, long capacity, int single);
+long artemis_sim_record_rows(artemis_sim_t *sim, long id);
+long artemis_sim_record_read(artemis_sim_t *sim, long id, long *cycle_out, double *time_out, double *dt_out, void *values_out, int clear);
+int artemis_sim_record_destroy(artemis_sim_t *sim, long id);
+
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured
  * with HIP events on the compute stream. */

@@ -62,6 +62,41 @@ int artemis_hip_locate_points(const artemis_pack_t *p, const void *table_dev, co
 int artemis_hip_sample_fields(const artemis_pack_t *p, long npoints, const int *loc_dev, const long *order_dev, int nsel,
                               const int *sel, int single, void *out_dev, void *stream);
 
+/* ---- a time series of samples, recorded inside the time loop ---------------------------------------------------------------
+ * A recorder appends, after a completed cycle that is due, one row {cycle, time, dt} and the [ncomp][npoints] sample of that
+ * moment to buffers on the device.  Both calls below can be captured into a graph: neither reads anything on the host, and
+ * what changes from cycle to cycle -- the row index, the cycle number, and the clock of the unsynchronised loop -- is read
+ * from device memory when the kernel runs, because a replayed graph has its arguments baked in.
+ *
+ * ctl_dev: one artemis_record_ctl_t; the caller zeroes it and sets `cycle` to the run's cycle count.  head_dev: `capacity`
+ * artemis_record_head_t.  rows_dev: [capacity][ncomp][npoints] doubles (floats with single != 0). */
+typedef struct artemis_record_ctl {
+  long long seen;    /* cycles ticked since the recorder was attached */
+  long long cycle;   /* the run's cycle count after the last tick */
+  long long rows;    /* rows in the buffers */
+  long long slot;    /* the row the last tick opened; -1: that cycle is not recorded */
+  long long dropped; /* due rows that found the buffers full (the caller sizes its batches so that this stays 0) */
+} artemis_record_ctl_t;
+typedef struct artemis_record_head {
+  long long cycle;
+  double time, dt; /* the time the row's values hold at; the next step's dt */
+} artemis_record_head_t;
+
+/* One thread: ++seen, ++cycle; the cycle is due if seen % every == 0.  A due cycle with rows < capacity opens slot = rows++
+ * and stores head[slot] = {cycle, time, dt}; a due cycle with rows == capacity counts in `dropped`; every other outcome
+ * leaves slot = -1.  time and dt are tstate_dev[0] and tstate_dev[1] (the device clock, after artemis_hip_advance_dt) when
+ * tstate_dev is not NULL, else the two arguments.  ARTEMIS_HIP_EINVAL: every < 1, capacity < 1, null ctl_dev or head_dev. */
+int artemis_hip_record_tick(void *ctl_dev, void *head_dev, const double *tstate_dev, double time, double dt, long every, long capacity,
+                            void *stream);
+
+/* artemis_hip_sample_fields of the same arguments into rows_dev + slot * ncomp * npoints, slot read from ctl_dev by the
+ * kernel (one scalar load per wave); a workgroup returns at once when slot < 0 or slot >= capacity.  The same bits as
+ * artemis_hip_sample_fields; ctl is only read, so the result does not depend on the launch shape.  The refusals of
+ * artemis_hip_sample_fields, and capacity < 1 and null ctl_dev or rows_dev; npoints == 0 or no components: succeeds, touches
+ * nothing. */
+int artemis_hip_record_samples(const artemis_pack_t *p, long npoints, const int *loc_dev, const long *order_dev, int nsel, const int *sel,
+                               int single, const void *ctl_dev, long capacity, void *rows_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
