@@ -246,6 +246,9 @@ def load():
         "artemis_hip_sample_fields": (i, [PPk, C.c_long, vp, vp, i, C.POINTER(i), i, vp, vp]),
         "artemis_hip_record_tick": (i, [vp, vp, vp, d, d, C.c_long, C.c_long, vp]),
         "artemis_hip_record_samples": (i, [PPk, C.c_long, vp, vp, i, C.POINTER(i), i, vp, C.c_long, vp, vp]),
+        "artemis_hip_record_integrals_scratch_bytes": (C.c_size_t, [PPk, i]),
+        "artemis_hip_record_integrals": (i, [PPk, i, vp, vp, vp, C.c_long, vp, vp]),
+        "artemis_hip_record_nbody": (i, [vp, vp, C.c_long, vp, C.c_long, vp, vp]),
         "artemis_hip_apply_bc": (i, [PPk, C.POINTER(i), C.POINTER(BcParams), vp]),
         "artemis_hip_external_gravity": (i, [PPk, C.POINTER(Gravity), d, d, vp]),
         "artemis_hip_rotating_frame_force": (i, [PPk, d, d, d, d, vp]),
@@ -373,6 +376,8 @@ EXPORTS_HIP = [
 # ... and the point-sampling entry points, which include/artemis_hip_sample.h declares (a header of its own beside artemis_hip.h)
 EXPORTS_HIP_SAMPLE = ["artemis_hip_locate_table_bytes", "artemis_hip_locate_table_build", "artemis_hip_locate_points",
                       "artemis_hip_sample_fields", "artemis_hip_record_tick", "artemis_hip_record_samples"]
+# ... and the recorded integrals and n-body sums of include/artemis_hip_record.h, its sibling
+EXPORTS_HIP_RECORD = ["artemis_hip_record_integrals_scratch_bytes", "artemis_hip_record_integrals", "artemis_hip_record_nbody"]
 
 
 def source_sha():

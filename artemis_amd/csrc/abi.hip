@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "kernels_record.hpp"
 #include "kernels_sample.hpp"
 #include "locate_table.hpp"
 #include "fields_shape.hpp"
@@ -482,6 +483,43 @@ int artemis_hip_record_samples(const artemis_pack_t *p, long npoints, const int 
   if (reinterpret_cast<uintptr_t>(loc_dev) % 16) return fail(ARTEMIS_HIP_EINVAL, "record samples: loc_dev is aligned to 16 bytes");
   artemis::launch_record_samples(artemis::make_pack_view(*p), npoints, loc_dev, order_dev, F, single != 0, ctl_dev, capacity, rows_dev, S(stream));
   return after_launch("record_samples");
+}
+
+// include/artemis_hip_record.h: what artemis_hip_record_integrals refuses of the pack and the window count ("" if nothing)
+static const char *record_integrals_refusal(const artemis_pack_t *p, int nwin) {
+  if (nwin < 0 || nwin > artemis::RECORD_MAX_WINDOWS) return "record integrals: 0 to 7 windows are taken";
+  if ((p->gas.nspecies && !p->gas.prim) || (p->dust.nspecies && !p->dust.prim))
+    return "record integrals: the primitive tables of every fluid in the pack are required";
+  return "";
+}
+size_t artemis_hip_record_integrals_scratch_bytes(const artemis_pack_t *p, int nwin) {
+  if (!p || p->nblocks < 1 || p->nx1 < 1 || p->nx2 < 1 || p->nx3 < 1 || p->gas.nspecies < 0 || p->dust.nspecies < 0) return 0;
+  if (nwin < 0 || nwin > artemis::RECORD_MAX_WINDOWS) return 0;
+  const size_t nq = 6 * static_cast<size_t>(p->gas.nspecies) + 4 * static_cast<size_t>(p->dust.nspecies);
+  return static_cast<size_t>(artemis::history_workgroups(artemis::make_pack_view(*p))) * (1 + static_cast<size_t>(nwin)) * nq * sizeof(double);
+}
+int artemis_hip_record_integrals(const artemis_pack_t *p, int nwin, const int *window_zones_dev, double *scratch_dev, const void *ctl_dev,
+                                 long capacity, double *rows_dev, void *stream) {
+  if (int rc = validate(p)) return rc;
+  const char *bad = record_integrals_refusal(p, nwin);
+  if (*bad) return fail(ARTEMIS_HIP_EINVAL, "%s", bad);
+  if (nwin > 0 && !window_zones_dev) return fail(ARTEMIS_HIP_EINVAL, "record integrals: %d windows without a table of their zones", nwin);
+  if (capacity < 1) return fail(ARTEMIS_HIP_EINVAL, "record integrals: capacity = %ld", capacity);
+  if (!scratch_dev || !ctl_dev || !rows_dev) return fail(ARTEMIS_HIP_EINVAL, "record integrals: null scratch_dev, ctl_dev or rows_dev");
+  if (reinterpret_cast<uintptr_t>(ctl_dev) % 8) return fail(ARTEMIS_HIP_EINVAL, "record integrals: ctl_dev is aligned to 8 bytes");
+  if (p->gas.nspecies + p->dust.nspecies == 0) return 0;
+  artemis::launch_record_integrals(artemis::make_pack_view(*p), nwin, window_zones_dev, scratch_dev, ctl_dev, capacity, rows_dev, S(stream));
+  return after_launch("record_integrals");
+}
+int artemis_hip_record_nbody(const double *base_dev, const double *acc_dev, long n, const void *ctl_dev, long capacity, double *rows_dev,
+                             void *stream) {
+  if (n < 0) return fail(ARTEMIS_HIP_EINVAL, "record nbody: n = %ld", n);
+  if (capacity < 1) return fail(ARTEMIS_HIP_EINVAL, "record nbody: capacity = %ld", capacity);
+  if (!base_dev || !acc_dev || !ctl_dev || !rows_dev) return fail(ARTEMIS_HIP_EINVAL, "record nbody: null base_dev, acc_dev, ctl_dev or rows_dev");
+  if (reinterpret_cast<uintptr_t>(ctl_dev) % 8) return fail(ARTEMIS_HIP_EINVAL, "record nbody: ctl_dev is aligned to 8 bytes");
+  if (n == 0) return 0;
+  artemis::launch_record_nbody(base_dev, acc_dev, n, ctl_dev, capacity, rows_dev, S(stream));
+  return after_launch("record_nbody");
 }
 
 int artemis_hip_estimate_dt(const artemis_pack_t *p, int fluid, double cfl, double *dt_out,

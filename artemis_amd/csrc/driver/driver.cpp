@@ -524,6 +524,7 @@ struct artemis_sim_impl {
   int history(double *out);
   DevBuf hist_sums, hist_scratch; // artemis_hip_history_sums: its result and its rows of partial sums, sized for this pack
   int history_device(double *out);
+  void history_host_sums(int nwin, const int *zones, double *out);
   // artemis_sim_gather_fields*: the device staging buffer of the artemis_hip_* field kernels -- a whole number of blocks
   // and at most FIELDS_STAGE_MB (default 256) MiB, one block where a block is larger; allocated by the first gather.
   // field_work: the work buffer of the reducing kernels, allocated by the first gather that needs one
@@ -3515,6 +3516,45 @@ int artemis_sim_impl::history(double *out) {
   return nout;
 }
 
+// The rank-local host loop behind history_device and behind the host fallback of an integral recorder (record.cpp):
+// out[1 + nwin][nq], set 0 over every interior zone, set 1 + w over the zones of zones[b][w] = {i0, i1, j0, j1, k0, k1}
+// (half-open, interior-relative).  One loop, so that set 0 of a recorded row has the bits of history_device by construction.
+void artemis_sim_impl::history_host_sums(int nwin, const int *zones, double *out) {
+  const int nsg = do_gas ? ns_gas : 0, nsd = do_dust ? ns_dust : 0;
+  const int nq = 6 * nsg + 4 * nsd;
+  for (int q = 0; q < (1 + nwin) * nq; ++q) out[q] = 0.0;
+  materialise_cons();
+  for (int b = 0; b < nb; ++b) {
+    std::vector<Real> g, d;
+    if (nsg) g = download(gu0, b);
+    if (nsd) d = download(du0, b);
+    for (int k = ks; k <= ke; ++k)
+      for (int j = js; j <= je; ++j)
+        for (int i = is; i <= ie; ++i) {
+          const Real vv = cell_coords(b, k, j, i).volume();
+          const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
+          for (int s = 0; s <= nwin; ++s) {
+            if (s > 0) {
+              const int *z = zones + (static_cast<size_t>(b) * nwin + (s - 1)) * 6;
+              const int ir = i - is, jr = j - js, kr = k - ks;
+              if (ir < z[0] || ir >= z[1] || jr < z[2] || jr >= z[3] || kr < z[4] || kr >= z[5]) continue;
+            }
+            double *o = out + static_cast<size_t>(s) * nq;
+            for (int n = 0; n < nsg; ++n) {
+              o[6 * n] += g[n * N + c] * vv;
+              for (int q = 0; q < 3; ++q) o[6 * n + 1 + q] += g[(nsg + 3 * n + q) * N + c] * vv;
+              o[6 * n + 4] += g[(4 * nsg + n) * N + c] * vv;
+              o[6 * n + 5] += g[(5 * nsg + n) * N + c] * vv;
+            }
+            for (int n = 0; n < nsd; ++n) {
+              o[6 * nsg + 4 * n] += d[n * N + c] * vv;
+              for (int q = 0; q < 3; ++q) o[6 * nsg + 4 * n + 1 + q] += d[(nsd + 3 * n + q) * N + c] * vv;
+            }
+          }
+        }
+  }
+}
+
 // The same integrals for every species, out = [mass, mom1..3, energy, internal energy] per gas species, then [mass,
 // mom1..3] per dust species: summed on the device from the primitives (kernels_history.hip; nothing is materialised or
 // downloaded but the sums), or -- a library without that kernel -- by history()'s host loop over all species.
@@ -3532,28 +3572,7 @@ int artemis_sim_impl::history_device(double *out) {
     CK(artemis_rt_memcpy_d2h(out, hist_sums.p, static_cast<size_t>(nout) * sizeof(double), stream), "d2h");
     CK(artemis_rt_stream_sync(stream), "sync");
   } else {
-    materialise_cons();
-    for (int b = 0; b < nb; ++b) {
-      std::vector<Real> g, d;
-      if (nsg) g = download(gu0, b);
-      if (nsd) d = download(du0, b);
-      for (int k = ks; k <= ke; ++k)
-        for (int j = js; j <= je; ++j)
-          for (int i = is; i <= ie; ++i) {
-            const Real vv = cell_coords(b, k, j, i).volume();
-            const size_t c = (static_cast<size_t>(k) * nj + j) * ni + i;
-            for (int n = 0; n < nsg; ++n) {
-              out[6 * n] += g[n * N + c] * vv;
-              for (int q = 0; q < 3; ++q) out[6 * n + 1 + q] += g[(nsg + 3 * n + q) * N + c] * vv;
-              out[6 * n + 4] += g[(4 * nsg + n) * N + c] * vv;
-              out[6 * n + 5] += g[(5 * nsg + n) * N + c] * vv;
-            }
-            for (int n = 0; n < nsd; ++n) {
-              out[6 * nsg + 4 * n] += d[n * N + c] * vv;
-              for (int q = 0; q < 3; ++q) out[6 * nsg + 4 * n + 1 + q] += d[(nsd + 3 * n + q) * N + c] * vv;
-            }
-          }
-    }
+    history_host_sums(0, nullptr, out);
   }
   if (has_comm && nranks > 1 && comm.allreduce_sum(comm.ctx, out, nout)) throw std::runtime_error("allreduce failed");
   return nout;
@@ -4387,6 +4406,15 @@ void host_components(artemis_sim_t *sim, int b, const std::vector<int> &codes, c
 // What record.cpp reaches of the handle (record_hooks.hpp; the rest goes through sample_hooks.hpp)
 namespace artemis_record {
 State *&state_of(artemis_sim_t *sim) { return sim->records; }
+NBodyRows nbody_of(artemis_sim_t *sim) {
+  const artemis_sim_impl &S = *sim->p;
+  NBodyRows r;
+  r.npart = static_cast<int>(S.particles.size());
+  r.host_rows = S.particle_force.data();
+  r.acc_dev = S.nb_force_dev.p;
+  return r;
+}
+void host_integrals(artemis_sim_t *sim, int nwin, const int *zones, double *out) { sim->p->history_host_sums(nwin, zones, out); }
 } // namespace artemis_record
 
 extern "C" {

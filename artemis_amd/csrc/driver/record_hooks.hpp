@@ -12,6 +12,18 @@ struct State; // the recorders of a handle (record.cpp)
 
 // ---- driver.cpp ------------------------------------------------------------------------------------------------------
 State *&state_of(artemis_sim_t *sim);
+// The n-body force rows of this rank: the host rows [npart][7] (what a flush adds the device accumulators to) and the
+// accumulators on the device, NULL while the run keeps none there.  npart == 0: a deck without particles.
+struct NBodyRows {
+  int npart = 0;
+  const double *host_rows = nullptr;
+  const double *acc_dev = nullptr;
+};
+NBodyRows nbody_of(artemis_sim_t *sim);
+// Host fallback of an integral recorder: out[1 + nwin][nq], the rank-local host sum behind artemis_sim_history_device (the
+// same loop, the same order of additions, no reduction over the ranks) over every interior zone (set 0) and over the zones
+// of zones[b][w] = {i0, i1, j0, j1, k0, k1} (set 1 + w; half-open, interior-relative).
+void host_integrals(artemis_sim_t *sim, int nwin, const int *zones, double *out);
 
 // ---- record.cpp: the time loop's side ----------------------------------------------------------------------------------
 void destroy(State *st);

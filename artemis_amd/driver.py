@@ -282,6 +282,12 @@ def _declare(L):
     L.artemis_sim_record_read.restype = l
     L.artemis_sim_record_read.argtypes = [vp, l, vp, vp, vp, vp, i]
     L.artemis_sim_record_destroy.argtypes = [vp, l]
+    L.artemis_sim_record_integrals_create.restype = l
+    L.artemis_sim_record_integrals_create.argtypes = [vp, l, l, i, vp, i]
+    L.artemis_sim_record_integrals_read.restype = l
+    L.artemis_sim_record_integrals_read.argtypes = [vp, l, vp, vp, vp, vp, vp, i]
+    L.artemis_sim_record_integrals_window_zones.restype = l
+    L.artemis_sim_record_integrals_window_zones.argtypes = [vp, l, vp]
     L._sim_declared = True
 
 
@@ -419,6 +425,100 @@ class Recorder:
             self.sim.L.artemis_sim_record_destroy(self.sim.h, self.id)
             if self._owns_plan:
                 self.plan.close()
+        self.id = None
+
+
+class IntegralSeries:
+    """What IntegralRecorder.read returns: cycle [n] int64, time [n], dt [n], integrals [n, 1 + nwin, nq] float64 and nbody
+    [n, npart, 7] (None for a recorder without n-body rows)"""
+
+    def __init__(self, cycle, time, dt, integrals, nbody):
+        self.cycle, self.time, self.dt, self.integrals, self.nbody = cycle, time, dt, integrals, nbody
+
+
+_HST_GAS = ("gas_mass", "gas_momentum_x1", "gas_momentum_x2", "gas_momentum_x3", "gas_energy", "gas_internal_energy")
+_HST_DUST = ("dust_mass", "dust_momentum_x1", "dust_momentum_x2", "dust_momentum_x3")
+
+
+class IntegralRecorder:
+    """A time series of the history integrals -- of this rank's mesh (set 0) and of up to seven windows (set 1 + w) -- and,
+    with nbody=True, of the n-body force sums, recorded on the device inside evolve() (Simulation.record_integrals makes
+    one).  Set 0 of a row is, on one rank, what history_device() would return had evolve returned after that cycle, bit for
+    bit; the n-body rows what nbody_force() would return if called for the first time there.  Rank-local, not part of a
+    checkpoint; recording flushes nothing and does not disturb the run.  labels[i] names entry i of a set as an hst file
+    names that column; the order is the history_device layout (species outermost), not the file's column order."""
+
+    def __init__(self, sim, every, capacity, windows, nbody):
+        self.sim, self.id, self.nbody = sim, None, bool(nbody)
+        self.windows = np.ascontiguousarray(np.zeros((0, 3, 2)) if windows is None else windows, dtype=np.float64)
+        if self.windows.ndim != 3 or self.windows.shape[1:] != (3, 2):
+            raise ValueError("windows: an [nwin, 3, 2] array of [lo, hi) per direction, not %r" % (self.windows.shape,))
+        self.nwin = len(self.windows)
+        if self.nwin > 7:
+            raise ValueError("%d windows: at most 7" % self.nwin)
+        L, h = sim.L, sim.h
+        self.nq = 6 * sim.ns_gas + 4 * sim.ns_dust
+        self.npart = L.artemis_sim_nbody_force(h, None, 0) if self.nbody else 0
+        if capacity is None:
+            row = 8 * ((1 + self.nwin) * self.nq + 7 * self.npart)
+            capacity = max(1, min(RECORD_DEFAULT_ROWS, RECORD_DEFAULT_BYTES // max(row, 1)))
+        self.every, self.capacity = int(every), int(capacity)
+        rid = L.artemis_sim_record_integrals_create(h, self.every, self.capacity, self.nwin, self.windows.ctypes.data if self.nwin else None,
+                                                    int(self.nbody))
+        if rid < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        self.id = rid
+        if L.artemis_sim_record_integrals_read(h, rid, None, None, None, None, None, 0) != self.nq:  # (no buffer: the size query)
+            self.close()
+            raise RuntimeError("the driver's integrals per set are not 6 ns_gas + 4 ns_dust")
+        # labels[i]: the hst column label of entry i (the strings artemis_amd.history.read_history yields), in the order of the
+        # history_device layout -- species outermost -- not in the file's column order, which is quantity outermost
+        self.labels = ["%s_%d" % (name, n) for n in range(sim.ns_gas) for name in _HST_GAS] + \
+                      ["%s_%d" % (name, n) for n in range(sim.ns_dust) for name in _HST_DUST]
+
+    def _live(self):
+        if self.id is None or not getattr(self.sim, "h", None):
+            raise RuntimeError("the recorder is closed")
+
+    @property
+    def rows(self):
+        """rows recorded so far and not cleared by read(clear=True); waits for the device and empties its buffers first"""
+        self._live()
+        n = self.sim.L.artemis_sim_record_rows(self.sim.h, self.id)
+        if n < 0:
+            raise RuntimeError(self.sim.L.artemis_sim_last_error().decode())
+        return n
+
+    def read(self, clear=False):
+        """An IntegralSeries of the rows so far, oldest first; clear=True forgets them afterwards (the counters go on)."""
+        n = self.rows
+        L, h = self.sim.L, self.sim.h
+        cycle, time, dt = np.empty(n, dtype=np.int64), np.empty(n), np.empty(n)
+        ni, nb = n * (1 + self.nwin) * self.nq, n * self.npart * 7
+        integrals, nbody = np.empty(max(ni, 1)), np.empty(max(nb, 1))  # (never empty: NULL is "no buffer")
+        if L.artemis_sim_record_integrals_read(h, self.id, cycle.ctypes.data if n else None, time.ctypes.data if n else None,
+                                               dt.ctypes.data if n else None, integrals.ctypes.data, nbody.ctypes.data, int(bool(clear))) < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        return IntegralSeries(cycle, time, dt, integrals[:ni].reshape(n, 1 + self.nwin, self.nq),
+                              nbody[:nb].reshape(n, self.npart, 7) if self.nbody else None)
+
+    def window_zones(self):
+        """[nblocks, nwin, 6] int32: the zones {i0, i1, j0, j1, k0, k1} of every window on every local block of the current
+        mesh, half-open and relative to the block's first interior zone; an empty range has i0 == i1"""
+        self._live()
+        L, h = self.sim.L, self.sim.h
+        nb = L.artemis_sim_record_integrals_window_zones(h, self.id, None)
+        if nb < 0:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        out = np.zeros((nb, self.nwin, 6), dtype=np.int32)
+        if out.size and L.artemis_sim_record_integrals_window_zones(h, self.id, out.ctypes.data) != nb:
+            raise RuntimeError(L.artemis_sim_last_error().decode())
+        return out
+
+    def close(self):
+        """Free the recorder; every later use raises RuntimeError."""
+        if self.id is not None and getattr(self.sim, "h", None):
+            self.sim.L.artemis_sim_record_destroy(self.sim.h, self.id)
         self.id = None
 
 
@@ -832,6 +932,22 @@ class Simulation:
         except Exception:
             plan.close()
             raise
+
+    def record_integrals(self, every=1, capacity=None, windows=None, nbody=False):
+        """An IntegralRecorder: after every `every`-th cycle that evolve() completes from now on, one row {cycle, time, dt,
+        integrals [1 + nwin, nq], nbody [npart, 7]} is taken ON THE DEVICE through the same tick as record().  Set 0 is the
+        history integrals of this rank's mesh -- what history_device() would return there, bit for bit on one rank -- and set
+        1 + w those of window w: windows is an [nwin, 3, 2] array (at most 7) of boxes [lo, hi) in the mesh's own coordinates,
+        an annular sector on a cylindrical mesh; a zone belongs to a window when the midpoint of its faces lies in it along
+        every direction with more than one zone (rec.window_zones() shows the index ranges).  nbody=True adds the n-body
+        force sums, what nbody_force() would return if first called there; nothing is flushed.  capacity: as for record().
+        ValueError: every < 1, capacity < 1, a windows array of another shape or with more than 7 windows; RuntimeError: what
+        the driver refuses (a window with lo >= hi, nbody=True on a deck without particles)."""
+        if int(every) < 1:
+            raise ValueError("every = %r: at least 1" % (every,))
+        if capacity is not None and int(capacity) < 1:
+            raise ValueError("capacity = %r: at least 1 row" % (capacity,))
+        return IntegralRecorder(self, every, capacity, windows, nbody)
 
     # the complete forms a dump may hold, in the order load_fields prefers them
     _GAS_FORMS = (("gas.prim.density", "gas.prim.velocity", "gas.prim.sie"),

@@ -385,6 +385,35 @@ long artemis_sim_record_rows(artemis_sim_t *sim, long id);
 long artemis_sim_record_read(artemis_sim_t *sim, long id, long *cycle_out, double *time_out, double *dt_out, void *values_out, int clear);
 int artemis_sim_record_destroy(artemis_sim_t *sim, long id);
 
+/* ---- a time series of the history integrals and of the n-body force sums, through the same tick.  An integral recorder is a
+ * recorder of a second kind: no plan, but nwin windows (0 .. 7) and a flag nbody; every, capacity, seen, due rows, drains and
+ * the undisturbed run are those of a sample recorder, and _rows and _destroy above serve both kinds (one id space).  A row:
+ *   cycle, time, dt            as above;
+ *   integrals[1 + nwin][nq]    nq = 6 ns_gas + 4 ns_dust in the layout of artemis_sim_history_device.  Set 0 is this rank's
+ *                              mesh: on one rank the bits artemis_sim_history_device would return had evolve returned after
+ *                              exactly that cycle (artemis_hip_history_sums on this rank's pack).  Set 1 + w is window w by
+ *                              the same pass and the same reduction tree (include/artemis_hip_record.h): a window that holds
+ *                              every zone has the bits of set 0, one that holds none is +0.0;
+ *   nbody[npart][7]            with nbody != 0: the host's force rows plus this rank's device accumulators -- on one rank the
+ *                              bits artemis_sim_nbody_force would return if called for the first time after exactly that
+ *                              cycle.  Recording flushes nothing, so later artemis_sim_nbody_force results keep their bits.
+ * windows: [nwin][3][2] doubles, the box [lo_d, hi_d) of each window in the mesh's own coordinates (an annular sector on a
+ * cylindrical mesh).  A zone belongs to a window when along every direction with more than one zone the midpoint of its two
+ * face positions, as the block's geometry holds them, satisfies lo_d <= c_d < hi_d; other directions are ignored, nothing
+ * wraps.  The host turns the windows into index ranges per block once per mesh epoch (after a remesh they are rebuilt, as a
+ * plan locates again); the device compares indices only.  Rows are rank-local; not part of a checkpoint; only evolve records.
+ *   _create        the recorder's id (>= 0), or -1: every < 1, capacity < 1, nwin outside 0 .. 7, a window with lo >= hi along
+ *                  a direction with more than one zone, nbody != 0 on a deck without particles
+ *   _read          all pointers NULL: nq.  Else the rows so far, oldest first -- integrals_out [rows][1 + nwin][nq], nbody_out
+ *                  [rows][npart][7] (ignored without n-body rows) -- and, with clear != 0, forgets them.  Returns nq, -1 on failure
+ *   _window_zones  zones_out [nblocks][nwin][6] ints {i0, i1, j0, j1, k0, k1}: the zones of every window on every local block,
+ *                  half-open and relative to the block's first interior zone, empty as i0 == i1 (NULL: nothing is copied).
+ *                  Returns the number of local blocks, -1 on failure */
+long artemis_sim_record_integrals_create(artemis_sim_t *sim, long every, long capacity, int nwin, const double *windows, int nbody);
+long artemis_sim_record_integrals_read(artemis_sim_t *sim, long id, long *cycle_out, double *time_out, double *dt_out, double *integrals_out,
+                                       double *nbody_out, int clear);
+long artemis_sim_record_integrals_window_zones(artemis_sim_t *sim, long id, int *zones_out);
+
 /* Seconds spent inside the timed region of the last artemis_sim_evolve (device-synchronised
  * at both ends), and the average duration in ms of the dominant kernel's launches measured
  * with HIP events on the compute stream. */
